@@ -17,6 +17,7 @@ region.  Synthetic SMPL-like body, procedural pose track, synthetic field
    127.0.0.1 and fails loudly when fewer than N devices exist.)
   python bench.py --gpus N --train-only   # train it/s (configs 2/4) as the headline line
   python bench.py --gpus 2 --dry-run      # launch / sharding / reduction plumbing on gloo, no kernels
+  python bench.py ... --dump-outputs DIR  # also write the last timed frame's outputs as DIR/<name>.npy (render paths)
 
 Prints ONE JSON line (rank 0).
 """
@@ -69,7 +70,37 @@ def parse():
     ap.add_argument("--train-steps", type=int, default=None,
                     help="training iterations timed after the render loop (0 = skip).  Default: 100 on one GPU; 0 on several -- the "
                          "frames/s line of a scaling run must not depend on a second workload (use --train-only, or pass a count)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step rendered (rank 0: rgb, depth, alpha, counter of its "
+                         "frame, float32) as DIR/<name>.npy -- at most 64 MB, a fixed pixel sample of larger frames.  The timed "
+                         "frames draw their random numbers from a generator seeded right before the timed region, so the same "
+                         "arguments give the same inputs (pose, occupancy-probe jitter) on every run (render paths only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    if args.dump_outputs and (args.train_only or args.dry_run):
+        ap.error("--dump-outputs writes a rendered frame: not available with --train-only / --dry-run")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes `arrays` ({name: tensor of one frame, leading dims [..., H, W(, C)]}) as out_dir/<name>.npy in float32.  If they
+    exceed DUMP_MAX_BYTES together, the same fixed, seeded sample of pixels is taken from each (sorted flat pixel indices,
+    written as pixel_index.npy in float64).  Returns {name: shape} of what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n_pix = next(iter(host.values())).shape[1] * next(iter(host.values())).shape[2]
+    per_pix = sum(a.size // n_pix for a in host.values()) * 4
+    if per_pix * n_pix > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.RandomState(0).choice(n_pix, (DUMP_MAX_BYTES - (1 << 20)) // (per_pix + 8), replace=False))
+        host = {k: a.reshape(a.shape[0], n_pix, -1)[:, keep].reshape((a.shape[0], len(keep)) + a.shape[3:]) for k, a in host.items()}
+        host["pixel_index"] = keep.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in host.items()}
 
 
 def cpu_baseline(body, fp, model, poses, tr, res, n_frames):
@@ -708,6 +739,10 @@ def main():
         if world_size > 1:
             torch.distributed.barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            dumped = {"dir": args.dump_outputs, "frame": (args.warmup + args.steps - 1) % len(poses),
+                      "arrays": dump_outputs(args.dump_outputs, dict(zip(("rgb", "depth", "alpha", "counter"), out)))}
         ranks = rank_report(rank, world_size, dev, {"rows": list(shard_rows(res, rank, world_size)), "alpha_coverage_whole_frame": float((out[2] > 0.5).float().mean())})
         if rank == 0:
             print(json.dumps({"metric": "novel_pose_frame_latency_frames_per_sec_%dx%d_row_sharded" % (res, res), "value": args.steps / dt, "unit": "frames/s",
@@ -716,7 +751,7 @@ def main():
                               "config": {"workload": "render_image_fast %dx%d, ONE frame at a time split by image rows over %d rank(s) (occupancy build on "
                                                      "every rank, row blocks all-gathered), eager launches, aist_demo.npz[:200]" % (res, res, world_size),
                                          "rows_per_rank": [list(shard_rows(res, r, world_size)) for r in range(world_size)]},
-                              "ranks": ranks}))
+                              "ranks": ranks, "dump_outputs": dumped}))
         if world_size > 1:
             torch.distributed.destroy_process_group()
         return
@@ -851,12 +886,13 @@ def main():
         _lib.check(L.ia_frame_stats(_lib.ptr(counter), _lib.ptr(alpha), counter.numel(), stat_acc[k].data_ptr(), _lib.stream()), "ia_frame_stats")
 
     frames_done = [0]
+    last_out = [None]
 
     def run_frames(i0, n):
         """the loop body of the timed region (frame + the two statistics reductions, executed on the frame's stream), used
         unchanged by the spin-up windows and the warm-up, so that nothing is executed for the first time inside the timed region"""
         for i in range(i0, i0 + n):
-            frame(i, stats)
+            last_out[0] = frame(i, stats)[0]
             frames_done[0] += 1
 
     # Adaptive spin-up, untimed but REPORTED.  A GPU that idled through model construction, the first
@@ -880,6 +916,10 @@ def main():
     spinup_ms = (time.perf_counter() - t_spin) * 1e3
     run_frames(0, args.warmup)
     torch.cuda.synchronize()
+    # the number of spin-up windows depends on timing: the timed frames' random draws (occupancy-probe jitter) start from a fixed
+    # seed instead, so that the same arguments give the timed frames the same inputs
+    torch.cuda.manual_seed(1234 + rank)
+    rng_start = torch.cuda.get_rng_state()
     stat_acc.zero_()
     if world_size > 1:
         torch.distributed.barrier()
@@ -892,6 +932,10 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # the last timed frame, copied out before anything else replays its graph replica (outputs of a replayed graph are static buffers)
+    last_frame = [t.clone() for t in last_out[0]] if args.dump_outputs and rank == 0 else None
+    last_call = graphed.calls - 1 if graphed is not None else None
+    rng_end = torch.cuda.get_rng_state()
     dt_local = dt                               # this rank's own clock around its K frames (the line reports the MAX over ranks)
     timed_frames = int(frames_done[0])          # what THIS rank rendered inside the timed region (the secondary runs below count on)
     main_samples_per_ray = float(cnt_sum.sum().item()) / args.steps
@@ -906,6 +950,23 @@ def main():
             eager_frame(args.warmup)
         torch.cuda.synchronize()
         dt += time.perf_counter() - t_re
+    dumped = None
+    if last_frame is not None:
+        redone = graphed is not None and last_call in graphed.incomplete_calls
+        if redone:
+            # the graph held too few wave-front iterations for the last frame: its result is the eager render, with the random
+            # draws its replay consumed (every timed frame advanced the generator's philox offset by the same amount)
+            seed, off0 = rng_start.view(torch.int64).tolist()
+            seed_end, off1 = rng_end.view(torch.int64).tolist()
+            assert seed_end == seed and (off1 - off0) % args.steps == 0, (seed, seed_end, off0, off1)
+            keep = torch.cuda.get_rng_state()
+            torch.cuda.set_rng_state(torch.tensor([seed, off1 - (off1 - off0) // args.steps], dtype=torch.int64).view(torch.uint8))
+            last_frame = list(eager_frame(args.warmup + args.steps - 1)[0])
+            torch.cuda.synchronize()
+            torch.cuda.set_rng_state(keep)
+        dumped = {"dir": args.dump_outputs, "frame": int(my[(args.warmup + args.steps - 1) % n_total] % len(poses)),
+                  "rerendered_eagerly": bool(redone),
+                  "arrays": dump_outputs(args.dump_outputs, dict(zip(("rgb", "depth", "alpha", "counter"), last_frame)))}
     # with several frames in flight the per-frame LATENCY is not ms_per_step: replay ONE replica's graph back to back
     one_fps = None
     if graphed is not None and args.in_flight > 1:
@@ -1078,6 +1139,7 @@ def main():
         "value_first_window": windows[0] * world_size, "value_steady": float(np.mean(windows[-3:])) * world_size,
         "frames_rerendered_eagerly": int(incomplete),
         "ms_per_step_instrumented": (dt_prof / args.steps * 1e3) if dt_prof else None,
+        "dump_outputs": dumped,
     }
     result["ranks"] = rank_report(rank, world_size, dev, {"frames_timed": int(timed_frames), "frames_per_s_local_clock": timed_frames / dt_local,
                                                            "launch_mode": mode, "frames_in_flight": (args.in_flight if graphed is not None else 1)})
