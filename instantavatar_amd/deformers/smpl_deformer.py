@@ -147,7 +147,7 @@ class SMPLDeformer():
     force_dense_train = False
 
     def fused_train_route(self):
-        """the training render over compact samples (Raymarcher.render_train_fused_smpl): one frame per step, on the GPU"""
+        """the training render over compact samples (Raymarcher.render_train_fused): one frame per step, on the GPU"""
         return not self.force_dense_train and torch.is_tensor(getattr(self, "vertices", None)) and self.vertices.is_cuda and self.vertices.shape[0] == 1
 
     def prepare_deformer(self, smpl_params):

@@ -21,6 +21,7 @@ import torch
 
 from . import _opt
 from .. import _lib
+from ..training import DeferredCount, field_autograd
 from .fast_snarf.forward_deformer import ForwardDeformer
 from .smplx import SMPL
 
@@ -163,6 +164,7 @@ class SNARFDeformer():
         self.opt = opt
         self.dtype = torch.float32
         self._ws = None
+        self._cand_counts = DeferredCount()
 
     def clone_shared(self):
         """A second deformer for the same subject: body model, weight voxels and rest-pose constants shared by reference,
@@ -170,6 +172,7 @@ class SNARFDeformer():
         assert self.initialized, "clone_shared: initialise the deformer first"
         other = SNARFDeformer.__new__(SNARFDeformer)
         other.body_model, other.opt, other.dtype, other._ws = self.body_model, self.opt, self.dtype, None
+        other._cand_counts = DeferredCount()
         other.deformer = self.deformer.clone_shared()
         other.initialized = True
         for k in ("tfs_inv_t", "vs_template", "bbox", "_joints_rest", "_parents32"):
@@ -412,33 +415,18 @@ class SNARFDeformer():
             return False
         return self.deformer.version == 1 or not self.tfs.requires_grad
 
-    #: number of `query_train_fused` calls whose candidates exceeded the capacity (they were dropped); the
-    #: capacity doubles after every such call (deferred check, see `_cand_count_check`)
+    #: number of `query_train_fused` calls whose candidates exceeded the capacity (they were dropped in compaction order --
+    #: the densities had holes); the capacity doubles after every such call (deferred check, `_cand_count_check`)
     train_overflow = 0
 
-    def _cand_count_post(self, n_cand, cap):
-        """copy the device-side candidate count to pinned memory without blocking; looked at by the next call"""
-        if not hasattr(self, "_cc_host"):
-            self._cc_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self._cc_host.copy_(n_cand, non_blocking=True)
-        self._cc_event = torch.cuda.Event()
-        self._cc_event.record()
-        self._cc_cap = cap
-
     def _cand_count_check(self):
-        """Deferred overflow check of the previous `query_train_fused` call (that call has long finished: no
-        stall).  An overflowing call dropped candidates in compaction order -- its densities had holes; it is
-        counted in `train_overflow` and the capacity grows so that it cannot happen twice at that size."""
-        ev = getattr(self, "_cc_event", None)
-        if ev is None:
-            return
-        ev.synchronize()
-        self._cc_event = None
-        self.last_cand_count = int(self._cc_host[0])
-        if self.last_cand_count > self._cc_cap:
-            self.train_overflow += 1
-            if self.train_cand_capacity is not None:
-                self.train_cand_capacity = max(self.train_cand_capacity, 2 * self.last_cand_count)
+        """Deferred overflow check of the previous `query_train_fused` call (no stall: that call has long finished)."""
+        self._cand_counts.check(self)
+
+    @property
+    def last_cand_count(self):
+        """candidates of the last `query_train_fused` call looked at, None before the first"""
+        return self._cand_counts.last[0] if self._cand_counts.last else None
 
     def query_train_fused(self, pts, net):
         """deform_train (snarf_deformer.py:143-159) without the dense [P,13,*] temporaries:
@@ -453,9 +441,8 @@ class SNARFDeformer():
         want_J_inv = self.tfs.requires_grad and torch.is_grad_enabled() and self.deformer.version == 1
         with torch.no_grad():
             sc = self.search_compact(pts, cap=cap, want_J_inv=want_J_inv)
-        from ..training import field_autograd
         rgb_c, sig_c = field_autograd(net, self.candidates_with_grad(sc), n_dev=sc["n_cand"])
-        self._cand_count_post(sc["n_cand"], cap)
+        self._cand_counts.post(sc["n_cand"], cap)
         arg = torch.empty(P, dtype=torch.int32, device=pts.device)
         sig_d = sig_c.detach().float().contiguous()
         _lib.check(_lib.lib().ia_candidate_argmax(_lib.ptr(sig_d), cap, _lib.ptr(sc["pt_off"]), _lib.ptr(sc["pt_cnt"]), P, k,

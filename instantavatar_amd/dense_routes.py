@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .training import active_step
 
 
 def _flat_rays(rays):
@@ -84,7 +85,8 @@ def composite_train(sigma, dists):
 
 def render_train(renderer, rays, model, noise, bg_color):
     """Training render with MAX_SAMPLES slots per ray (dense): marcher -> jitter -> callable on the occupied slots ->
-    (+ sigma noise) -> differentiable compositing in torch ops.  `renderer.train_draws` may inject the random draws."""
+    (+ sigma noise) -> differentiable compositing in torch ops.  Inside a training step the random draws may be injected
+    (`training.StepState.draws`)."""
     L = _lib.lib()
     _lib.require_cuda(rays.o)
     o, d, near, far = _flat_rays(rays)
@@ -97,7 +99,8 @@ def render_train(renderer, rays, model, noise, bg_color):
         _lib.check(L.ia_raymarch_train(_lib.ptr(o.detach()), _lib.ptr(d.detach()), _lib.ptr(near.detach()), _lib.ptr(far.detach()), n,
                                        _lib.ptr(grid.occ_bits), C.byref(occ), _lib.ptr(step.detach()), S, _lib.ptr(z), _lib.stream()), "ia_raymarch_train")
     occupied = z > 0
-    draws = getattr(renderer, "train_draws", None) or {}
+    state = active_step()
+    draws = state.draws if state is not None else {}
     draw = lambda key, make: draws[key].to(z).reshape(z.shape) if key in draws else make(z)
     z = z + draw("ray_jitter", torch.rand_like) * step[:, None]
     pts = z[..., None] * d[:, None] + o[:, None]

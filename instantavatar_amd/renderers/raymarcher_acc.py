@@ -19,6 +19,7 @@ import torch
 
 from .. import _lib
 from ..models.structures.density_grid import DensityGrid
+from ..training import DeferredCount, ZeroPool, active_step, field_autograd, pooled_zeros
 
 
 def _find_native_pair(model):
@@ -120,12 +121,11 @@ class _CompositeTrainFn(torch.autograd.Function):
         dev = cand_rgb.device
         n, S = st["n"], st["S"]
         cand_rgb, cand_sigma = cand_rgb.contiguous(), cand_sigma.contiguous()
-        cap = st["s_z"].shape[0]
-        from ..training import pooled_zeros
+        cap, pool = st["s_z"].shape[0], st["pool"]
         color, depth, alpha = torch.empty((n, 3), device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
-        weights = pooled_zeros((n, S), dev)  # the kernel writes the occupied slots only
-        # the zero-initialised gradient buffers of the backward pass, taken now from the step's zero pool (one fill launch for all)
-        ctx.d_bufs = (pooled_zeros((cand_sigma.shape[0], 3), dev), pooled_zeros((cand_sigma.shape[0],), dev))
+        weights = pooled_zeros(pool, (n, S), dev)  # the kernel writes the occupied slots only
+        # the zero-initialised gradient buffers of the backward pass, taken now from the render's zero pool (one fill launch for all)
+        ctx.d_bufs = (pooled_zeros(pool, (cand_sigma.shape[0], 3), dev), pooled_zeros(pool, (cand_sigma.shape[0],), dev))
         ctx.set_materialize_grads(False)   # an unused output (depth) arrives as None, not as a freshly filled zero tensor
         sv = dict(arg=torch.empty(cap, dtype=torch.int32, device=dev), sigma=torch.empty(cap, device=dev),
                   alpha=torch.empty(cap, device=dev), T=torch.empty(cap, device=dev))
@@ -177,6 +177,7 @@ class Raymarcher(torch.nn.Module):
         self._iters_hint = 8     # loop iterations enqueued per call; adapted per frame
         self._n_alive_host = None
         self.last_iters = 0
+        self._counts = DeferredCount(index=1)   # [samples, candidates] of the last fused training render
 
     def initialize(self, N):
         """raymarcher_acc.py:66-70: one training grid (N with smpl_init: one per frame), held in a PLAIN list as in the
@@ -280,12 +281,23 @@ class Raymarcher(torch.nn.Module):
         }
 
     # ----------------------------------------------------------------- train
-    def render_train_fused_smpl(self, rays, deformer, net, noise, bg_color):
-        """render_train (raymarcher_acc.py:140-186) with the SMPLDeformer plugin (fit stage) over COMPACT samples: march + jitter +
-        compaction, nearest-vertex deformation + compaction of the valid samples (`ia_smpl_nn_compact`), the field under autograd
-        on them, compositing forward / backward as two kernels.  With the SMPL parameters under optimisation the gradient reaches
-        the per-vertex transforms (`ia_smpl_nn_compact_bwd` -> `ia_smpl_lbs_bwd`) and, through the sample points, the rays
-        (`ia_ray_samples_bwd` -> transform_rays_w2s's autograd -> w2s).  No host synchronisation."""
+    def render_train_fused(self, rays, deformer, net, noise, bg_color):
+        """render_train (raymarcher_acc.py:140-186) over COMPACT samples: march + jitter + compaction, deformation of the
+        samples, the field under autograd on the surviving candidates, compositing forward / backward as two kernels.  No host
+        synchronisation: all counts stay on the device.  The deformation stage depends on the deformer:
+          * SNARFDeformer: candidate search + compaction (`search_compact`), up to k candidates per sample in a buffer of
+            `train_cand_capacity`; with tfs under optimisation (refinement) the candidates carry the implicit-differentiation
+            gradient to tfs (deformer_torch.py:50-67).  The counts of step i are copied to pinned memory and looked at during
+            step i+1: a step whose candidates exceeded the capacity (they were dropped) is counted in `train_overflow` and the
+            capacity grows for the following steps;
+          * SMPLDeformer (fit stage): nearest-vertex deformation + compaction of the valid samples (`ia_smpl_nn_compact`), one
+            candidate per sample at most, so nothing can overflow.  With the SMPL parameters under optimisation the gradient
+            reaches the per-vertex transforms (`ia_smpl_nn_compact_bwd` -> `ia_smpl_lbs_bwd`) and, through the sample points,
+            the rays (`ia_ray_samples_bwd` -> transform_rays_w2s's autograd -> w2s).
+        Under grad the render opens a zero pool for its zero-initialised work tensors (`training.ZeroPool`).  Inside a training
+        step (`training.StepState`) the random draws come from the step, and the pool and the overflow source go to it."""
+        from ..deformers.smpl_deformer import SMPLDeformer
+        smpl = isinstance(deformer, SMPLDeformer)
         L = _lib.lib()
         dev = rays.o.device
         o = rays.o.reshape(-1, 3).float().contiguous()
@@ -294,99 +306,52 @@ class Raymarcher(torch.nn.Module):
         far = rays.far.detach().reshape(-1).float().contiguous()
         n, S = o.shape[0], self.MAX_SAMPLES
         cap = n * S
-        grid = self.density_grid_train
-        occ = self._occ_desc_cached(grid)
+        k = 1 if smpl else len(deformer.deformer.init_bones)
+        cand_cap = cap if smpl else min(cap * k, self.train_cand_capacity)
+        step = active_step()
+        draws = step.draws if step is not None else {}                          # injected by reproducible tests
+        draw = lambda key, make: draws[key].to(dev).float().reshape(n, S).contiguous() if key in draws else make((n, S), device=dev)
+        # ONE zero-fill for the zero-initialised work tensors: (SNARF) the two device counters, field outputs [V,3] + [V], dense
+        # weights [n,S], the compositor's candidate gradients [V,3] + [V], the loss values
+        pool = ZeroPool(8 * cand_cap + n * S + (1024 if smpl else 2048), dev) if torch.is_grad_enabled() else None
+        if step is not None:
+            step.pool = pool
         i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+        # (SNARF: the step's two device-side counters as ONE int32 pair [samples, candidates], zeroed with the pool, copied to the
+        #  host in one transfer; the SMPL route's march kernel zeroes its sample counter itself)
+        counts = None if smpl else pooled_zeros(pool, (2,), dev).view(torch.int32)
         st = dict(s_pts=torch.empty((cap, 3), device=dev), s_z=torch.empty(cap, device=dev), s_slot=i32(cap),
-                  ray_off=i32(n), ray_cnt=i32(n), n_samples=i32(1), near=near, far=far, n=n, S=S)
-        draws = getattr(self, "train_draws", None) or {}
-        jitter = draws["ray_jitter"].to(dev).float().reshape(n, S).contiguous() if "ray_jitter" in draws else torch.rand((n, S), device=dev)  # :156
-        with torch.no_grad():
-            _lib.check(L.ia_march_train_compact(_lib.ptr(o.detach()), _lib.ptr(d.detach()), _lib.ptr(near), _lib.ptr(far), n, _lib.ptr(grid.occ_bits),
-                                                C.byref(occ), S, _lib.ptr(jitter), _lib.ptr(st["s_pts"]), _lib.ptr(st["s_z"]),
-                                                _lib.ptr(st["s_slot"]), _lib.ptr(st["ray_off"]), _lib.ptr(st["ray_cnt"]),
-                                                _lib.ptr(st["n_samples"]), cap, _lib.stream()), "ia_march_train_compact")
-        pts = st["s_pts"]
-        if torch.is_grad_enabled() and (o.requires_grad or d.requires_grad):
-            pts = _RaySamplesFn.apply(o, d, st)
-        T_inv = deformer.T_inv
-        from ..training import ZeroPool, field_autograd
-        if torch.is_grad_enabled():
-            ZeroPool.current = ZeroPool(8 * cap + n * S + 1024, dev)
-        if torch.is_grad_enabled() and (pts.requires_grad or T_inv.requires_grad):
-            cand = _SmplDeformCompactFn.apply(pts, T_inv, deformer, st["n_samples"], st)
-        else:
-            with torch.no_grad():
-                cand = _SmplDeformCompactFn.apply(pts, T_inv, deformer, st["n_samples"], st)
-        st.update(n_init=1, bg=bg_color.reshape(-1, 3).float().contiguous() if bg_color is not None else None,
-                  noise=(draws["noise"].to(dev).float().reshape(n, S).contiguous() if "noise" in draws else torch.randn((n, S), device=dev))
-                  if noise > 0 else None, noise_scale=float(noise))                # :167
-        rgb_c, sig_c = field_autograd(net, cand, n_dev=st["n_cand"])
-        self.train_overflow_flag = None      # one candidate per sample at most: the sample capacity bounds the candidates
-        self.train_overflow_src = None
-        color, depth, alpha, weights = _CompositeTrainFn.apply(rgb_c.float(), sig_c.float(), st)
-        return {
-            "rgb_coarse": color.reshape(rays.o.shape),
-            "depth_coarse": depth.reshape(rays.near.shape),
-            "alpha_coarse": alpha.reshape(rays.near.shape),
-            "weight_coarse": weights.reshape(*rays.near.shape, -1),
-        }
-
-    def render_train_fused(self, rays, deformer, net, noise, bg_color):
-        """render_train (raymarcher_acc.py:140-186) over COMPACT samples: march + jitter +
-        compaction, candidate search + compaction, field under autograd on the surviving
-        candidates, compositing forward/backward as two kernels.  No host synchronisation: all
-        counts stay on the device."""
-        L = _lib.lib()
-        dev = rays.o.device
-        o = rays.o.reshape(-1, 3).float().contiguous()
-        d = rays.d.reshape(-1, 3).float().contiguous()
-        near = rays.near.reshape(-1).float().contiguous()
-        far = rays.far.reshape(-1).float().contiguous()
-        n, S = o.shape[0], self.MAX_SAMPLES
-        cap = n * S
+                  ray_off=i32(n), ray_cnt=i32(n), n_samples=i32(1) if smpl else counts[0:1], near=near, far=far, n=n, S=S,
+                  pool=pool)
+        jitter = draw("ray_jitter", torch.rand)                                   # :156
         grid = self.density_grid_train
-        occ = self._occ_desc_cached(grid)
-        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
-        k = len(deformer.deformer.init_bones)
-        cand_cap = min(cap * k, self.train_cand_capacity)
-        from ..training import ZeroPool, field_autograd, pooled_zeros
-        if torch.is_grad_enabled():
-            # ONE zero-fill for the step's zero-initialised work tensors (closed by training_step): the two device counters,
-            # field outputs [V,3] + [V], dense weights [n,S], the compositor's candidate gradients [V,3] + [V], the loss values
-            ZeroPool.current = ZeroPool(8 * cand_cap + n * S + 2048, dev)
-        # the step's two device-side counters as ONE int32 pair: [samples, candidates] -- zeroed with the pool, copied to the host
-        # in one transfer (`_train_counts_post`)
-        counts = pooled_zeros((2,), dev).view(torch.int32)
-        st = dict(s_pts=torch.empty((cap, 3), device=dev), s_z=torch.empty(cap, device=dev), s_slot=i32(cap),
-                  ray_off=i32(n), ray_cnt=i32(n), n_samples=counts[0:1], near=near, far=far, n=n, S=S)
-        draws = getattr(self, "train_draws", None) or {}                           # injected by reproducible tests
-        jitter = draws["ray_jitter"].to(dev).float().reshape(n, S).contiguous() if "ray_jitter" in draws else torch.rand((n, S), device=dev)  # :156
-        want_J_inv = deformer.tfs.requires_grad and torch.is_grad_enabled() and deformer.deformer.version == 1
         with torch.no_grad():
             _lib.check(L.ia_march_train_compact(_lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), n, _lib.ptr(grid.occ_bits),
-                                                C.byref(occ), S, _lib.ptr(jitter), _lib.ptr(st["s_pts"]), _lib.ptr(st["s_z"]),
-                                                _lib.ptr(st["s_slot"]), _lib.ptr(st["ray_off"]), _lib.ptr(st["ray_cnt"]),
-                                                _lib.ptr(st["n_samples"]), cap, _lib.stream()), "ia_march_train_compact")
-            sc = deformer.search_compact(st["s_pts"], n_pts_dev=st["n_samples"], cap=cand_cap,
-                                         want_J_inv=want_J_inv, n_cand_out=counts[1:2])
-        # No host read: the field runs on a capacity-sized candidate buffer with the device-side
-        # count (kernels clamp to it).  The counts of step i are copied to pinned memory and looked
-        # at during step i+1: a step whose candidates exceeded the capacity (they were dropped) is
-        # counted in `train_overflow` and the capacity grows for the following steps.
-        self._train_counts_check()
-        st.update(pt_off=sc["pt_off"], pt_cnt=sc["pt_cnt"], n_init=k,
-                  bg=bg_color.reshape(-1, 3).float().contiguous() if bg_color is not None else None,
-                  noise=(draws["noise"].to(dev).float().reshape(n, S).contiguous() if "noise" in draws else torch.randn((n, S), device=dev))
-                  if noise > 0 else None, noise_scale=float(noise))                # :167
-        # (SMPL refinement: the candidates carry the implicit-differentiation gradient to tfs, deformer_torch.py:50-67)
-        rgb_c, sig_c = field_autograd(net, deformer.candidates_with_grad(sc), n_dev=sc["n_cand"])
-        self._train_counts_post(counts, cand_cap)
-        # device-side overflow flag of THIS step: candidates past the capacity were dropped (in atomic-arrival order), so the
-        # step's gradients are wrong -- `training_step` feeds the flag to the optimiser's found_inf, the update is skipped on
-        # the device without a host read; the deferred count check then grows the capacity and the next steps are whole
-        self.train_overflow_flag = None
-        self.train_overflow_src = (sc["n_cand"], int(cand_cap))     # -> `training_step` (the loss kernel compares; `overflow_flag()` for others)
+                                                C.byref(self._occ_desc_cached(grid)), S, _lib.ptr(jitter), _lib.ptr(st["s_pts"]),
+                                                _lib.ptr(st["s_z"]), _lib.ptr(st["s_slot"]), _lib.ptr(st["ray_off"]),
+                                                _lib.ptr(st["ray_cnt"]), _lib.ptr(st["n_samples"]), cap, _lib.stream()),
+                       "ia_march_train_compact")
+        if smpl:
+            pts = _RaySamplesFn.apply(o, d, st)
+            cand = _SmplDeformCompactFn.apply(pts, deformer.T_inv, deformer, st["n_samples"], st)
+            n_cand = st["n_cand"]
+        else:
+            want_J_inv = deformer.tfs.requires_grad and torch.is_grad_enabled() and deformer.deformer.version == 1
+            with torch.no_grad():
+                sc = deformer.search_compact(st["s_pts"], n_pts_dev=st["n_samples"], cap=cand_cap, want_J_inv=want_J_inv,
+                                             n_cand_out=counts[1:2])
+            self._train_counts_check()
+            st.update(pt_off=sc["pt_off"], pt_cnt=sc["pt_cnt"])
+            cand, n_cand = deformer.candidates_with_grad(sc), sc["n_cand"]
+        st.update(n_init=k, bg=bg_color.reshape(-1, 3).float().contiguous() if bg_color is not None else None,
+                  noise=draw("noise", torch.randn) if noise > 0 else None, noise_scale=float(noise))      # :167
+        rgb_c, sig_c = field_autograd(net, cand, n_dev=n_cand, pool=pool)
+        if not smpl:
+            self._counts.post(counts, cand_cap, record=not getattr(self, "_graph_capture", False))
+            if step is not None:
+                # candidates past the capacity were dropped (in atomic-arrival order), so the step's gradients are wrong: the loss
+                # kernel compares the counter with the capacity and the update is skipped on the device, without a host read
+                step.overflow_src = (n_cand, int(cand_cap))
         color, depth, alpha, weights = _CompositeTrainFn.apply(rgb_c.float(), sig_c.float(), st)
         return {
             "rgb_coarse": color.reshape(rays.o.shape),
@@ -398,54 +363,21 @@ class Raymarcher(torch.nn.Module):
     #: capacity (candidates) of the training field call; 2^20 x 480 B of activations = 0.5 GB
     train_cand_capacity = 1 << 20
     train_overflow = 0
-    train_overflow_flag = None     # device scalar > 0: the last training render dropped candidates (set by callers / tests)
-    train_overflow_src = None      # (device int32 candidate counter, capacity) of the last fused training render
-
-    def overflow_flag(self):
-        """The overflow flag of the last training render as a device float scalar (None: the route cannot overflow)."""
-        if self.train_overflow_flag is not None:
-            return self.train_overflow_flag
-        if self.train_overflow_src is not None:
-            cnt, cap = self.train_overflow_src
-            return (cnt.reshape(-1)[0] > cap).to(torch.float32).reshape(())
-        return None
-
-    def _train_counts_post(self, counts, cand_cap):
-        """counts: device int32 [2] = [samples, candidates] of this step -> pinned host pair, one asynchronous copy"""
-        if not hasattr(self, "_tc_host"):
-            self._tc_host = torch.zeros(2, dtype=torch.int32).pin_memory()
-        self._tc_host.copy_(counts, non_blocking=True)
-        if getattr(self, "_graph_capture", False):
-            return   # recorded into a graph: the replaying caller marks the copy with `_train_counts_posted`
-        self._train_counts_posted(cand_cap)
-
-    def _train_counts_posted(self, cand_cap):
-        self._tc_event = torch.cuda.Event()
-        self._tc_event.record()
-        self._tc_cap = cand_cap
-
-    def _train_counts_peek(self, cand_cap):
-        """Graph-replay variant of the deferred check: look at whatever counts the device has copied to the pinned
-        pair so far -- those of a step one or two replays back -- without waiting for anything."""
-        if not hasattr(self, "_tc_host"):
-            return
-        self.last_train_counts = (int(self._tc_host[0]), int(self._tc_host[1]))
-        if self.last_train_counts[1] > cand_cap:
-            self.train_overflow += 1
-            self.train_cand_capacity = max(self.train_cand_capacity, 2 * self.last_train_counts[1])
-            self._tc_host[1] = 0   # counted once
 
     def _train_counts_check(self):
-        """Deferred look at the previous step's counts (no stall: that step has long finished)."""
-        ev = getattr(self, "_tc_event", None)
-        if ev is None or getattr(self, "_graph_capture", False):
-            return
-        ev.synchronize()
-        self._tc_event = None
-        self.last_train_counts = (int(self._tc_host[0]), int(self._tc_host[1]))
-        if self.last_train_counts[1] > self._tc_cap:
-            self.train_overflow += 1
-            self.train_cand_capacity = max(self.train_cand_capacity, 2 * self.last_train_counts[1])
+        """Deferred look at the previous step's counts (no stall: that step has long finished; `training.DeferredCount`)."""
+        if not getattr(self, "_graph_capture", False):
+            self._counts.check(self)
+
+    def _train_counts_peek(self, cand_cap):
+        """Graph-replay variant of the deferred check: whatever counts the device has copied so far -- those of a step one
+        or two replays back -- without waiting for anything."""
+        self._counts.peek(self, cand_cap)
+
+    @property
+    def last_train_counts(self):
+        """(samples, candidates) of the last training render looked at, None before the first."""
+        return self._counts.last
 
     def iters_executed(self):
         """Wave-front iterations of the last fused test render that had rays to process (host read)."""
@@ -461,9 +393,6 @@ class Raymarcher(torch.nn.Module):
         """raymarcher_acc.py:140-186."""
         pair = self._fused or _find_native_pair(model)
         if pair is not None and rays.o.is_cuda and pair[0].fused_train_route():
-            from ..deformers.smpl_deformer import SMPLDeformer
-            if isinstance(pair[0], SMPLDeformer):
-                return self.render_train_fused_smpl(rays, pair[0], pair[1], noise, bg_color)
             return self.render_train_fused(rays, pair[0], pair[1], noise, bg_color)
         from .. import dense_routes
         return dense_routes.render_train(self, rays, model, noise, bg_color)   # any other callable / the dense deformer route

@@ -28,12 +28,12 @@ _MM_OUT_DTYPE = [None]
 
 
 class ZeroPool:
-    """The zero-initialised fp32 work tensors of ONE training step (field outputs past the live count, the dense weight
-    tensor the compositor fills sparsely, the candidate-gradient buffers of its backward, the five loss values) as slices of
+    """The zero-initialised fp32 work tensors of ONE training render (field outputs past the live count, the dense weight
+    tensor the compositor fills sparsely, the candidate-gradient buffers of its backward, the loss values) as slices of
     ONE buffer zero-filled by ONE launch: each of these was its own ~5 us fill kernel in a 2 ms step.  `Raymarcher.
-    render_train_fused` opens the pool (it knows the sizes), `training_step` closes it; outside a pool -- and for requests
-    the pool cannot serve -- `pooled_zeros` is `torch.zeros`."""
-    current = None
+    render_train_fused` opens a pool under grad (it knows the sizes) and hands it to the field and the compositor; inside a
+    training step it is also the step's pool (`StepState.pool`), where the loss kernel finds it.  Without a pool -- and for
+    requests the pool cannot serve -- `pooled_zeros` is `torch.zeros`."""
 
     def __init__(self, numel, device):
         self.buf = torch.zeros(int(numel), device=device)
@@ -50,14 +50,77 @@ class ZeroPool:
         return out
 
 
-def pooled_zeros(shape, device):
-    shape = tuple(shape) if isinstance(shape, (tuple, list, torch.Size)) else (int(shape),)
-    pool = ZeroPool.current
-    if pool is not None and pool.buf.device == torch.device(device):
-        t = pool.take(shape)
-        if t is not None:
-            return t
-    return torch.zeros(shape, device=device)
+def pooled_zeros(pool, shape, device):
+    t = pool.take(shape) if pool is not None and pool.buf.device == torch.device(device) else None
+    return t if t is not None else torch.zeros(shape, device=device)
+
+
+class StepState:
+    """The transient state of ONE `training_step`, alive exactly as long as the step: the injected random draws (in), the
+    zero pool of the step's training render (`ZeroPool`, opened by the renderer), and the render's overflow source (out:
+    device int32 candidate counter and the capacity of its buffers; None when the route cannot overflow).  Inside
+    `with StepState(draws):` it is the active step (`active_step()`): the renderer, `dense_routes.render_train` and the
+    loss kernel read it there."""
+
+    def __init__(self, draws=None):
+        self.draws, self.pool, self.overflow_src = draws or {}, None, None
+
+    def __enter__(self):
+        global _ACTIVE_STEP
+        _ACTIVE_STEP = self
+        return self
+
+    def __exit__(self, *exc):
+        global _ACTIVE_STEP
+        _ACTIVE_STEP = None
+
+
+_ACTIVE_STEP = None
+
+
+def active_step():
+    """The `StepState` of the training step being run; None outside one."""
+    return _ACTIVE_STEP
+
+
+class DeferredCount:
+    """A device-side int32 count (a candidate counter, or the [samples, candidates] pair of a training render) looked at
+    one call later, without a stall: `post` copies it to pinned memory behind the call's kernels; `check` waits for that
+    copy (long finished by then); `peek` (graph replay: the copy is a node of the replayed graph) reads whatever has
+    arrived without waiting.  Entry `index` above the capacity means candidates were dropped: the owner's
+    `train_overflow` counts it and its `train_cand_capacity` (None: unbounded) grows to twice the count."""
+
+    def __init__(self, index=0):
+        self.index, self.host, self.event, self.cap, self.last = index, None, None, None, None
+
+    def post(self, counts, cap, record=True):
+        """record=False: the copy is being captured into a graph; its replays are looked at with `peek`"""
+        if self.host is None:
+            self.host = torch.zeros(counts.numel(), dtype=torch.int32).pin_memory()
+        self.host.copy_(counts, non_blocking=True)
+        if record:
+            self.event, self.cap = torch.cuda.Event(), cap
+            self.event.record()
+
+    def check(self, owner):
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = None
+            self._grow(owner, self.cap)
+
+    def peek(self, owner, cap):
+        if self.host is not None and self._grow(owner, cap):
+            self.host[self.index] = 0       # counted once
+
+    def _grow(self, owner, cap):
+        self.last = tuple(int(v) for v in self.host)
+        count = self.last[self.index]
+        if count <= cap:
+            return False
+        owner.train_overflow += 1
+        if owner.train_cand_capacity is not None:
+            owner.train_cand_capacity = max(owner.train_cand_capacity, 2 * count)
+        return True
 
 
 def _mm_f32(a, b):
@@ -76,17 +139,17 @@ def _mm_f32(a, b):
 
 class _FieldFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, enc_params, col_params, net, n_dev):
+    def forward(ctx, x, enc_params, col_params, net, n_dev, pool):
         """n_dev: optional device int32[1] live count -- x is then a capacity-sized buffer whose
-        tail is never read; outputs past the count are zero."""
+        tail is never read; outputs past the count are zero (slices of `pool` when it can serve them)."""
         L = _lib.lib()
         xc = x.detach().reshape(-1, 3).float().contiguous()
         V = xc.shape[0]
         stride = L.ia_field_act_stride(net.n_levels)
         acts = torch.empty((V, stride), device=x.device, dtype=torch.float16)
-        alloc = pooled_zeros if n_dev is not None else (lambda shp, device: torch.empty(shp, device=device))
-        rgb = alloc((V, 3), device=x.device)
-        sigma = alloc((V,), device=x.device)
+        alloc = (lambda shp: pooled_zeros(pool, shp, x.device)) if n_dev is not None else (lambda shp: torch.empty(shp, device=x.device))
+        rgb = alloc((V, 3))
+        sigma = alloc((V,))
         desc = net.field_desc(V)
         split = desc.enc_split
         desc.enc_split = int(getattr(net, "enc_split_train", split))   # (the training batches' own XCD balance hint: see NeRFNGPNet)
@@ -160,7 +223,7 @@ class _FieldFn(torch.autograd.Function):
             _lib.check(L.ia_hashgrid_bwd(_lib.ptr(xc), V, _lib.ptr(ctx.n_dev), C.byref(net.field_desc()),
                                          _lib.ptr(dfeat), dtable.data_ptr(), _lib.ptr(dx), _lib.stream()),
                        "ia_hashgrid_bwd")
-        return dx, None, None, None, None
+        return dx, None, None, None, None, None
 
 
 def _scratch_grad(net, tag, p):
@@ -246,7 +309,7 @@ def _mlp_backward_gemm(net, acts, rgb, d_rgb, d_sigma, S, g_enc, g_col):
     return dfeat
 
 
-def field_autograd(net, x, n_dev=None):
+def field_autograd(net, x, n_dev=None, pool=None):
     if torch.is_grad_enabled() and (net.encoder.params.requires_grad or net.color_net.params.requires_grad or x.requires_grad):
         from . import parallel
         red = parallel.current_reducer()
@@ -254,23 +317,23 @@ def field_autograd(net, x, n_dev=None):
             # the LAST field backward of the step starts the bucketed all-reduce; only calls that are recorded into the
             # autograd graph are counted (a no-grad probe has no backward and would keep the count from reaching zero)
             red.field_forward()
-    return _FieldFn.apply(x, net.encoder.params, net.color_net.params, net, n_dev)
+    return _FieldFn.apply(x, net.encoder.params, net.color_net.params, net, n_dev, pool)
 
 
-def _nerf_loss_kernel(rgb, alpha, weight, tgt_rgb, tgt_alpha, w_rgb, w_alpha, w_reg, poison=None, overflow_src=None):
+def _nerf_loss_kernel(rgb, alpha, weight, tgt_rgb, tgt_alpha, w_rgb, w_alpha, w_reg, overflow_src=None):
     """`ia_nerf_loss`: (out = {loss, mse_loss, loss_alpha_coarse, reg_alpha, reg_density[, overflow]}, d_rgb, d_alpha, d_weight), flat.
     overflow_src = (device int32 counter [1], capacity): the kernel poisons the step itself when the counter exceeds the capacity
-    and reports that as the sixth value."""
+    and reports that as the sixth value.  `out` is a slice of the active training step's zero pool when there is one."""
     r, a, w = (t.detach().reshape(-1).float().contiguous() for t in (rgb, alpha, weight))
     tr, ta = tgt_rgb.detach().reshape(-1).float().contiguous(), tgt_alpha.detach().reshape(-1).float().contiguous()
-    out = pooled_zeros((6 if overflow_src is not None else 5,), r.device)
+    step = active_step()
+    out = pooled_zeros(step.pool if step is not None else None, (6 if overflow_src is not None else 5,), r.device)
     d_r, d_a, d_w = torch.empty_like(r), torch.empty_like(a), torch.empty_like(w)
-    pz = poison.detach().reshape(()).float().contiguous() if poison is not None else None
     cnt, cap = overflow_src if overflow_src is not None else (None, 0)
     if cnt is not None:
         assert cnt.dtype == torch.int32 and cnt.is_cuda and cnt.numel() >= 1, "overflow counter: device int32"
     _lib.check(_lib.lib().ia_nerf_loss(_lib.ptr(r), _lib.ptr(tr), _lib.ptr(a), _lib.ptr(ta), _lib.ptr(w), a.numel(),
-                                       w.numel(), w_rgb, w_alpha, w_reg, _lib.ptr(pz), _lib.ptr(cnt), int(cap), _lib.ptr(out),
+                                       w.numel(), w_rgb, w_alpha, w_reg, None, _lib.ptr(cnt), int(cap), _lib.ptr(out),
                                        _lib.ptr(d_r), _lib.ptr(d_a), _lib.ptr(d_w), _lib.stream()), "ia_nerf_loss")
     return out, d_r, d_a, d_w
 
@@ -314,14 +377,14 @@ class NeRFLoss(torch.nn.Module):
         """the loss is exactly the kernel's five terms (no LPIPS / depth term active): `value_and_grads` may replace autograd"""
         return bool(self.fused) and predicts["rgb_coarse"].is_cuda and type(self).forward is NeRFLoss.forward
 
-    def value_and_grads(self, predicts, targets, poison=None, overflow_src=None):
+    def value_and_grads(self, predicts, targets, overflow_src=None):
         """The losses (detached) and d loss / d (rgb_coarse, alpha_coarse, weight_coarse) straight from the kernel: the caller
         seeds autograd with them (`torch.autograd.backward(outputs, grads)`) instead of building loss -> mul -> backward out of
-        nine small launches.  poison: device scalar, > 0 = NaN loss and gradients; overflow_src = (device int32 counter,
-        capacity): the same decided inside the kernel, reported as losses["skipped_overflow"] (see `ia_nerf_loss`)."""
+        nine small launches.  overflow_src = (device int32 counter, capacity): a counter above the capacity turns the loss and
+        the gradients into NaN inside the kernel, reported as losses["skipped_overflow"] (see `ia_nerf_loss`)."""
         r, a, w = predicts["rgb_coarse"], predicts["alpha_coarse"], predicts["weight_coarse"]
         out, d_r, d_a, d_w = _nerf_loss_kernel(r, a, w, targets["rgb"], targets["alpha"], float(self.w_rgb), float(self.w_alpha),
-                                               float(self.w_reg), poison=poison, overflow_src=overflow_src)
+                                               float(self.w_reg), overflow_src=overflow_src)
         losses = {"mse_loss": out[1], "loss_alpha_coarse": out[2], "reg_alpha": out[3], "reg_density": out[4], "loss": out[0]}
         if overflow_src is not None:
             losses["skipped_overflow"] = out[5]
@@ -536,103 +599,101 @@ def training_step(model, batch, optimizer, loss_fn, world_size=1, is_refine=Fals
     `_capturing`: the call is being recorded into a HIP graph (GraphedTrainStep): nothing executes, so the
     host-side step counter is left alone.
     `draws`: optional dict of injected random tensors for reproducible tests -- `grid_jitter` [64,64,64,3]
-    (density_grid.py:47), `ray_jitter` [n_rays, MAX_SAMPLES] (raymarcher_acc.py:156), `noise` [n_rays, MAX_SAMPLES] (:167)."""
-    draws = draws or {}
-    from . import parallel
-    if getattr(model, "SMPL_param", None) is not None:            # DNeRF.py:113-128 (optimize_SMPL.enable)
-        batch = dict(batch)
-        idx_dev = batch.get("idx_dev")     # device copy of the frame index when the data side provides one (no H2D copy per step)
-        if idx_dev is None:
-            idx_dev = batch["idx"].reshape(-1).long().to(model.SMPL_param.betas.weight.device)
-        body_params = model.SMPL_param(idx_dev.reshape(-1).long())
-        for k in ("global_orient", "body_pose", "transl"):
-            batch[k] = body_params[k]
-        from .deformers.smpl_deformer import SMPLDeformer
-        if isinstance(model.deformer, SMPLDeformer):
-            batch["betas"] = body_params["betas"]
-        # near / far follow the refined translation (DNeRF.py:124-127: |transl| -/+ 1 for every ray): one launch
-        tr = batch["transl"].detach().reshape(-1)[:3].float().contiguous()
-        if tr.is_cuda and batch["near"].is_cuda:
-            near, far = torch.empty_like(batch["near"], dtype=torch.float32).contiguous(), torch.empty_like(batch["far"], dtype=torch.float32).contiguous()
-            _lib.check(_lib.lib().ia_near_far(_lib.ptr(tr), near.numel(), _lib.ptr(near), _lib.ptr(far), _lib.stream()), "ia_near_far")
-            batch["near"], batch["far"] = near, far
-        else:
-            dist = torch.norm(batch["transl"], dim=-1, keepdim=True).detach()
-            batch["near"] = (dist - 1).reshape(1, *([1] * (batch["near"].dim() - 1))).expand_as(batch["near"]).contiguous()
-            batch["far"] = (dist + 1).reshape(1, *([1] * (batch["far"].dim() - 1))).expand_as(batch["far"]).contiguous()
-    model.renderer.idx = int(batch["idx"][0]) if "idx" in batch else 0
-    from .deformers.snarf_deformer import SNARFDeformer
-    prep = model.deformer.prepare_deformer
-    if type(model.deformer) is SNARFDeformer and getattr(prep, "__func__", None) is SNARFDeformer.prepare_deformer:
-        prep(batch, want_bbox=False)   # no consumer of the deformed-voxel box in a training step (computed on demand otherwise)
-    else:                              # (another deformer plugin, or a caller's wrapper around the method)
-        prep(batch)
-    reducer = parallel.GradReducer(world_size)
-    parallel.set_current_reducer(reducer if reducer.active else None)
-    try:
-        reg = update_density_grid(model, world_size, jitter=draws.get("grid_jitter"), differentiable=not is_refine)
-        model.net_coarse.initialize(model.deformer.bbox)
-        use_noise = model.global_step < 1000 and not is_refine
-        model.renderer.train_draws = draws if draws else None
+    (density_grid.py:47), `ray_jitter` [n_rays, MAX_SAMPLES] (raymarcher_acc.py:156), `noise` [n_rays, MAX_SAMPLES] (:167).
+    What the step hands between the renderer and the loss -- these draws, the zero pool of the training render, the render's
+    overflow source -- lives in ONE `StepState`, the active step for exactly the duration of this call.  The loss values of an
+    eager step are copied out of the pool (one launch), so that a value the caller keeps does not keep the pool alive; a
+    captured step returns the pool's slices themselves (GraphedTrainStep's static outputs)."""
+    with StepState(draws) as step:
+        from . import parallel
+        if getattr(model, "SMPL_param", None) is not None:            # DNeRF.py:113-128 (optimize_SMPL.enable)
+            batch = dict(batch)
+            idx_dev = batch.get("idx_dev")     # device copy of the frame index when the data side provides one (no H2D copy per step)
+            if idx_dev is None:
+                idx_dev = batch["idx"].reshape(-1).long().to(model.SMPL_param.betas.weight.device)
+            body_params = model.SMPL_param(idx_dev.reshape(-1).long())
+            for k in ("global_orient", "body_pose", "transl"):
+                batch[k] = body_params[k]
+            from .deformers.smpl_deformer import SMPLDeformer
+            if isinstance(model.deformer, SMPLDeformer):
+                batch["betas"] = body_params["betas"]
+            # near / far follow the refined translation (DNeRF.py:124-127: |transl| -/+ 1 for every ray): one launch
+            tr = batch["transl"].detach().reshape(-1)[:3].float().contiguous()
+            if tr.is_cuda and batch["near"].is_cuda:
+                near, far = torch.empty_like(batch["near"], dtype=torch.float32).contiguous(), torch.empty_like(batch["far"], dtype=torch.float32).contiguous()
+                _lib.check(_lib.lib().ia_near_far(_lib.ptr(tr), near.numel(), _lib.ptr(near), _lib.ptr(far), _lib.stream()), "ia_near_far")
+                batch["near"], batch["far"] = near, far
+            else:
+                dist = torch.norm(batch["transl"], dim=-1, keepdim=True).detach()
+                batch["near"] = (dist - 1).reshape(1, *([1] * (batch["near"].dim() - 1))).expand_as(batch["near"]).contiguous()
+                batch["far"] = (dist + 1).reshape(1, *([1] * (batch["far"].dim() - 1))).expand_as(batch["far"]).contiguous()
+        model.renderer.idx = int(batch["idx"][0]) if "idx" in batch else 0
+        from .deformers.snarf_deformer import SNARFDeformer
+        prep = model.deformer.prepare_deformer
+        if type(model.deformer) is SNARFDeformer and getattr(prep, "__func__", None) is SNARFDeformer.prepare_deformer:
+            prep(batch, want_bbox=False)   # no consumer of the deformed-voxel box in a training step (computed on demand otherwise)
+        else:                              # (another deformer plugin, or a caller's wrapper around the method)
+            prep(batch)
+        reducer = parallel.GradReducer(world_size)
+        parallel.set_current_reducer(reducer if reducer.active else None)
         try:
+            reg = update_density_grid(model, world_size, jitter=step.draws.get("grid_jitter"), differentiable=not is_refine)
+            model.net_coarse.initialize(model.deformer.bbox)
+            use_noise = model.global_step < 1000 and not is_refine
             predicts = model.forward(batch, eval_mode=False, noise=1 if use_noise else 0)
+            # (the fused render leaves the SOURCE of its overflow flag -- its device-side candidate counter and the capacity of its
+            #  buffers -- instead of a flag tensor: the loss kernel of the direct path compares them itself, two launches less per step)
+            src = step.overflow_src
+            with_reg = reg is not None and not is_refine
+            direct = (not with_reg) and hasattr(loss_fn, "direct_backward_ok") and loss_fn.direct_backward_ok(predicts) and \
+                all(torch.is_tensor(predicts.get(k)) and predicts[k].requires_grad for k in ("rgb_coarse", "alpha_coarse", "weight_coarse"))
+            # a render that dropped candidates (capacity overflow) must not update anything, on ANY rank: its loss is turned
+            # into NaN before the backward pass, so every gradient of this rank is NaN, the gradient average carries that to
+            # all ranks, and the ordinary non-finite check skips the step everywhere -- no extra collective, no host read
+            if direct:
+                # the loss kernel already holds d loss / d (rgb, alpha, weights): seed autograd with them (and let the kernel do the
+                # NaN poisoning) instead of loss -> where -> mul -> backward -> foreach_mul: nine small launches less per step
+                losses, grads = loss_fn.value_and_grads(predicts, batch, overflow_src=src)
+                overflow = losses.get("skipped_overflow")     # (device scalar written by the loss kernel; also fed to the optimiser below)
+            else:
+                overflow = None if src is None else (src[0].reshape(-1)[0] > src[1]).to(torch.float32).reshape(())
+                losses = loss_fn(predicts, batch)
+                if with_reg:
+                    losses["reg"] = reg
+                    losses["loss"] = losses["loss"] + reg
+            if not getattr(optimizer, "grads_zeroed", False):   # (a FusedAdam step with fused_zero_grad left every buffer zero-filled)
+                optimizer.zero_grad(set_to_none=True)
+            if direct:
+                torch.autograd.backward([predicts["rgb_coarse"], predicts["alpha_coarse"], predicts["weight_coarse"]], list(grads))
+            else:
+                total = losses["loss"]
+                if overflow is not None:
+                    total = total * torch.where(overflow > 0, torch.full_like(overflow, float("nan")), torch.ones_like(overflow))
+                total.backward()
+            all_reduce_grads(model, world_size, reducer)
         finally:
-            model.renderer.train_draws = None
-        overflow = getattr(model.renderer, "train_overflow_flag", None)
-        # (the fused render leaves the SOURCE of the flag -- its device-side candidate counter and the capacity of its buffers --
-        #  instead of a flag tensor: the loss kernel of the direct path compares them itself, two launches less per step)
-        overflow_src = getattr(model.renderer, "train_overflow_src", None) if overflow is None else None
-        with_reg = reg is not None and not is_refine
-        direct = (not with_reg) and hasattr(loss_fn, "direct_backward_ok") and loss_fn.direct_backward_ok(predicts) and \
-            all(torch.is_tensor(predicts.get(k)) and predicts[k].requires_grad for k in ("rgb_coarse", "alpha_coarse", "weight_coarse"))
-        # a render that dropped candidates (capacity overflow) must not update anything, on ANY rank: its loss is turned
-        # into NaN before the backward pass, so every gradient of this rank is NaN, the gradient average carries that to
-        # all ranks, and the ordinary non-finite check skips the step everywhere -- no extra collective, no host read
-        if direct:
-            # the loss kernel already holds d loss / d (rgb, alpha, weights): seed autograd with them (and let the kernel do the
-            # NaN poisoning) instead of loss -> where -> mul -> backward -> foreach_mul: nine small launches less per step
-            losses, grads = loss_fn.value_and_grads(predicts, batch, poison=overflow, overflow_src=overflow_src)
-            if overflow_src is not None:
-                overflow = losses["skipped_overflow"]     # (device scalar written by the loss kernel; also fed to the optimiser below)
-        else:
-            if overflow_src is not None:
-                overflow = (overflow_src[0].reshape(-1)[0] > overflow_src[1]).to(torch.float32).reshape(())
-            losses = loss_fn(predicts, batch)
-            if with_reg:
-                losses["reg"] = reg
-                losses["loss"] = losses["loss"] + reg
-        if not getattr(optimizer, "grads_zeroed", False):   # (a FusedAdam step with fused_zero_grad left every buffer zero-filled)
-            optimizer.zero_grad(set_to_none=True)
-        if direct:
-            torch.autograd.backward([predicts["rgb_coarse"], predicts["alpha_coarse"], predicts["weight_coarse"]], list(grads))
-        else:
-            total = losses["loss"]
-            if overflow is not None:
-                total = total * torch.where(overflow > 0, torch.full_like(overflow, float("nan")), torch.ones_like(overflow))
-            total.backward()
-        all_reduce_grads(model, world_size, reducer)
-    finally:
-        parallel.set_current_reducer(None)
-        ZeroPool.current = None
-    params = [p for g in optimizer.param_groups for p in g["params"]]
-    model.renderer.train_overflow_flag = None
-    model.renderer.train_overflow_src = None
-    losses["skipped_non_finite"] = optimizer_step_skip_non_finite(optimizer, params, extra_flag=overflow)
-    if overflow is not None:
-        losses["skipped_overflow"] = overflow
-    if hasattr(model.net_coarse, "mark_updated"):
-        # refresh the fp16 shadow + MFMA fragments on next use (the fused optimiser step has already written the shadow of
-        # the network it was configured for: only the fragment image is rebuilt then)
-        if getattr(optimizer, "_shadow_owner", None) is model.net_coarse:
-            model.net_coarse.mark_updated(shadow_fresh=True)
-        else:
-            model.net_coarse.mark_updated()
-    if not _capturing:
-        model.global_step += 1
-    # nothing the caller gets keeps the autograd graph of this step alive (see SNARFDeformer.release_graph)
-    if hasattr(model.deformer, "release_graph"):
-        model.deformer.release_graph()
-    return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in losses.items()}
+            parallel.set_current_reducer(None)
+        params = [p for g in optimizer.param_groups for p in g["params"]]
+        losses["skipped_non_finite"] = optimizer_step_skip_non_finite(optimizer, params, extra_flag=overflow)
+        if overflow is not None:
+            losses["skipped_overflow"] = overflow
+        if hasattr(model.net_coarse, "mark_updated"):
+            # refresh the fp16 shadow + MFMA fragments on next use (the fused optimiser step has already written the shadow of
+            # the network it was configured for: only the fragment image is rebuilt then)
+            if getattr(optimizer, "_shadow_owner", None) is model.net_coarse:
+                model.net_coarse.mark_updated(shadow_fresh=True)
+            else:
+                model.net_coarse.mark_updated()
+        if not _capturing:
+            model.global_step += 1
+        # nothing the caller gets keeps the autograd graph of this step alive (see SNARFDeformer.release_graph)
+        if hasattr(model.deformer, "release_graph"):
+            model.deformer.release_graph()
+        losses = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in losses.items()}
+        if not _capturing:
+            keys = [k for k in ("loss", "mse_loss", "loss_alpha_coarse", "reg_alpha", "reg_density", "skipped_overflow") if k in losses]
+            losses.update(zip(keys, torch.stack([losses[k] for k in keys]).unbind()))
+        return losses
 
 
 class GraphedTrainStep:
@@ -651,9 +712,11 @@ class GraphedTrainStep:
     whose tensor shapes differ from the captured ones.  With several ranks the bucketed all-reduce is part of the captured
     graph (`graph_collectives`); every rank replays / runs eagerly at the same steps, so the collectives stay matched.  Models with a `SMPL_param` embedding (fit stage, refinement) are captured
     too: the frame index reaches the embedding tables as the device tensor `idx_dev` of the batch.  One graph is
-    held per (noise on/off, capacity) state; a candidate-capacity overflow (renderer.train_overflow) drops
-    the graphs so that they are captured again with the grown capacity.  Learning rates are turned into
-    device tensors, so that an `lr_scheduler` keeps working across replays."""
+    held per (noise on/off, capacity) state.  A replayed render copies its candidate counts to pinned memory; before
+    each replay `Raymarcher._train_counts_peek` looks at what has arrived, and a count above the capacity
+    (counted in renderer.train_overflow) grows `train_cand_capacity`: the graphs of the old capacity are dropped and the
+    step is captured again.  Learning rates are turned into device tensors, so that an `lr_scheduler` keeps working
+    across replays."""
 
     #: captured graphs kept alive (one per (noise, capacity, per-frame grid) state; each holds its own activation buffers)
     max_graphs = 256

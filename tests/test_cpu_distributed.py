@@ -326,7 +326,8 @@ def _train_worker(rank, world, port, q):
 
     def forward_with_overflow(b, eval_mode=False, noise=0):
         out = fwd(b, eval_mode=eval_mode, noise=noise)
-        model.renderer.train_overflow_flag = torch.tensor(1.0 if rank == 0 else 0.0)     # what render_train_fused sets
+        # what render_train_fused hands to the step: the candidate counter and the capacity of its buffers
+        training.active_step().overflow_src = (torch.tensor([1 if rank == 0 else 0], dtype=torch.int32), 0)
         return out
     model.forward = forward_with_overflow
     losses2 = training.training_step(model, batch, opt, loss_fn, world_size=world)

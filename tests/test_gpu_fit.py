@@ -48,7 +48,7 @@ def test_fit_stage_optimises_smpl_parameters_and_exports(tmp_path):
 
 @pytest.mark.parametrize("blend", [False, True], ids=["zero-blendshapes", "blendshapes"])
 def test_fit_fused_route_equals_dense_route(blend):
-    """The fit step's fused route -- `ia_smpl_lbs_fwd/_bwd` for the body model, `Raymarcher.render_train_fused_smpl` (compact
+    """The fit step's fused route -- `ia_smpl_lbs_fwd/_bwd` for the body model, `Raymarcher.render_train_fused` (SMPL route, compact
     samples, `ia_smpl_nn_compact[_bwd]`, `ia_ray_samples_bwd`) for the render -- against the route that keeps the reference's
     structure: SMPL.forward as lbs.py-style torch ops under autograd, dense [n_rays, 256] sample blocks, boolean-mask gathers
     (dense_routes.render_train + SMPLDeformer.deform_train).  Same state, same injected draws -> same losses, same gradients of

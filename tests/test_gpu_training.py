@@ -586,6 +586,34 @@ def test_render_candidate_overflow_skips_the_optimizer_step_on_the_device(gw):
     assert r.train_overflow >= 1 and r.train_cand_capacity > 512
 
 
+def test_step_state_and_zero_pool_end_with_their_step_or_render(gw):
+    """the loss values an eager `training_step` returns are copies, not slices of the step's zero pool (one kept
+    scalar would keep ~8 x cand_cap x 4 B alive), and a training render called directly, outside a step, leaves no active step
+    and no pool behind once its result and graph are dropped."""
+    import gc
+    import weakref
+    from instantavatar_amd.models.structures.utils import Rays
+    from instantavatar_amd.training import active_step
+    tmodel, batches = _train_setup(seed_model=9, n_rays=1024)
+    opt = configure_optimizer(tmodel)
+    loss_fn = NeRFLoss(dict(w_rgb=1.0, w_alpha=0.1, w_reg=0.1))
+    for it in range(2):     # step 0: occupancy update + regulariser (autograd route); step 1: loss gradients from the loss kernel
+        out = training_step(tmodel, batches[it], opt, loss_fn)
+        assert active_step() is None
+        for k in ("loss", "mse_loss", "loss_alpha_coarse", "reg_alpha", "reg_density", "skipped_overflow"):
+            assert out[k].untyped_storage().nbytes() <= 64, (it, k, out[k].untyped_storage().nbytes())
+    b = batches[2]
+    tmodel.deformer.prepare_deformer(b)
+    rays = Rays(o=b["rays_o"].clone(), d=b["rays_d"].clone(), near=b["near"].clone(), far=b["far"].clone())
+    tmodel.deformer.transform_rays_w2s(rays)
+    out = tmodel.renderer.render_train_fused(rays, tmodel.deformer, tmodel.net_coarse, 0, b["bg_color"])
+    assert out["weight_coarse"].requires_grad and out["weight_coarse"]._base is not None
+    pool = weakref.ref(out["weight_coarse"]._base)      # (the compositor's dense weights are a slice of the render's zero pool)
+    del out
+    gc.collect()
+    assert active_step() is None and pool() is None
+
+
 def test_non_finite_upstream_gradient_skips_the_step(gw):
     """one NaN in d_sigma must end in `skipped_non_finite` through the gradient scale (S = NaN), not through luck."""
     model = gw[0]
