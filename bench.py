@@ -9,7 +9,8 @@ Inputs (camera rays, SMPL poses, weights) are resident in HBM before the timed
 region.  Synthetic SMPL-like body, procedural pose track, synthetic field
 (see instantavatar_amd/synthetic.py): no dataset / checkpoint exists offline.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W          # the plain run: set-up, spin-up, W warm-up and K timed frames, the line
+  python bench.py --gpus N --steps K --warmup W --full   # + everything else the bench measures, after the timed frames (below)
   (N > 1: one rank per GPU over RCCL; frames are sharded across ranks, no data-path
    collective -> weak scaling.  Under torch.distributed.run the ranks read RANK /
    LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment; started directly with
@@ -18,6 +19,11 @@ region.  Synthetic SMPL-like body, procedural pose track, synthetic field
   python bench.py --gpus N --train-only   # train it/s (configs 2/4) as the headline line
   python bench.py --gpus 2 --dry-run      # launch / sharding / reduction plumbing on gloo, no kernels
   python bench.py ... --dump-outputs DIR  # also write the last timed frame's outputs as DIR/<name>.npy (render paths)
+
+A plain run does only what its headline needs (`metric`, `value`, `ms_per_step` and the statistics of the timed frames).
+--full adds, after the timed region and without touching it: the latency of one frame in flight, the procedural pose
+track, the instrumented pass with the roofline block and the counter summaries of profiles/, the isolated hash-grid
+lookup, the training legs (--train-steps) and the CPU baseline (--cpu-frames).  Both print the same headline.
 
 Prints ONE JSON line (rank 0).
 """
@@ -47,7 +53,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--res", type=int, default=512)
-    ap.add_argument("--cpu-frames", type=int, default=3, help="frames timed on the CPU oracle after one warm-up frame (0 = skip; minimum 3)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything else this file knows: one frame "
+                    "in flight, the procedural pose track, the instrumented pass + roofline, the isolated hash-grid lookup, training "
+                    "(--train-steps) and the CPU baseline (--cpu-frames).  Off by default: a plain run stops at its headline line")
+    ap.add_argument("--cpu-frames", type=int, default=None, help="with --full: frames timed on the CPU oracle after one warm-up frame "
+                    "(0 = skip; minimum 3; default 3)")
     ap.add_argument("--spinup-max-ms", type=float, default=4000.0,
                     help="upper bound of the adaptive, untimed and REPORTED spin-up: 10-frame windows are run until three "
                          "consecutive windows agree within 3 %% (reported as spinup_ms / value_first_window / value_steady)")
@@ -64,12 +74,14 @@ def parse():
                     "the N ranks (parallel.render_frame_tiled: occupancy build duplicated, blocks all-gathered over RCCL); strong scaling")
     ap.add_argument("--dry-run", action="store_true", help="no kernels: exercises launch, frame sharding and the "
                     "collectives on the gloo backend (CPU test of the N > 1 plumbing)")
-    ap.add_argument("--no-profile", action="store_true", help="disable the in-library event timing")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the instrumented pass (in-library event timing) and "
+                    "what is derived from it (roofline, isolated hash-grid lookup)")
     ap.add_argument("--no-graph", action="store_true", help="launch every frame eagerly instead of replaying the captured HIP "
                     "graph (eager: ~110 launches per frame from Python, a few hundred microseconds slower and jittery)")
     ap.add_argument("--train-steps", type=int, default=None,
-                    help="training iterations timed after the render loop (0 = skip).  Default: 100 on one GPU; 0 on several -- the "
-                         "frames/s line of a scaling run must not depend on a second workload (use --train-only, or pass a count)")
+                    help="with --full: training iterations timed after the render loop (0 = skip).  Default: 100 on one GPU; 0 on "
+                         "several -- the frames/s line of a scaling run must not depend on a second workload (use --train-only, or pass "
+                         "a count)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step rendered (rank 0: rgb, depth, alpha, counter of its "
                          "frame, float32) as DIR/<name>.npy -- at most 64 MB, a fixed pixel sample of larger frames.  The timed "
@@ -80,6 +92,14 @@ def parse():
         ap.error("--steps must be at least 1 (the number of timed steps)")
     if args.dump_outputs and (args.train_only or args.dry_run):
         ap.error("--dump-outputs writes a rendered frame: not available with --train-only / --dry-run")
+    if not args.full and ((args.train_steps or 0) > 0 or (args.cpu_frames or 0) > 0):
+        ap.error("--train-steps / --cpu-frames size parts of the --full run: pass --full with them (a plain run measures its headline only)")
+    if not args.full:
+        args.train_steps = args.cpu_frames = 0
+    if args.train_steps is None:
+        args.train_steps = 100 if args.gpus == 1 else 0
+    if args.cpu_frames is None:
+        args.cpu_frames = 3
     return args
 
 
@@ -655,8 +675,6 @@ def _profile_json(stem, tus):
 
 def main():
     args = parse()
-    if args.train_steps is None:
-        args.train_steps = 100 if args.gpus == 1 else 0
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch_distributed(args))
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -708,7 +726,6 @@ def main():
     n_total = args.steps + args.warmup
     track = os.path.join(ROOT, "tests", "golden", "aist_demo_200.npz")
     poses, tr = syn.load_animation_track(track)          # BASELINE config 3 / SURVEY 8(d): first 200 frames of aist_demo.npz
-    poses_proc, tr_proc = syn.procedural_pose_track(200)   # rounds 1-2 workload, secondary figure
 
     def max_over_ranks(x):
         if world_size > 1:
@@ -967,9 +984,11 @@ def main():
         dumped = {"dir": args.dump_outputs, "frame": int(my[(args.warmup + args.steps - 1) % n_total] % len(poses)),
                   "rerendered_eagerly": bool(redone),
                   "arrays": dump_outputs(args.dump_outputs, dict(zip(("rgb", "depth", "alpha", "counter"), last_frame)))}
+    # Everything from here to the result line is the --full run: measurements of their own, after the timed region and
+    # outside `value`.  A plain run skips them all.
     # with several frames in flight the per-frame LATENCY is not ms_per_step: replay ONE replica's graph back to back
     one_fps = None
-    if graphed is not None and args.in_flight > 1:
+    if args.full and graphed is not None and args.in_flight > 1:
         g0 = graphed.graphs[0]
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -983,37 +1002,39 @@ def main():
         one_fps = args.steps / (time.perf_counter() - t1)
         g0.finish()
     # secondary figure: the procedural pose track rounds 1-2 quoted, through the same graphs (untimed for `value`)
-    proc_track, dt2, err2, inc2 = None, 0.0, None, 0
-    n_sec = min(max(args.steps, 20), 100)
-    keep = (poses, tr, pose_t, tr_t)
-    try:
-        poses, tr = poses_proc, tr_proc
-        pose_t, tr_t = torch.as_tensor(poses, device=dev), torch.as_tensor(tr, device=dev)
-        run_frames(0, 10)
-        torch.cuda.synchronize()
-        stat_acc.zero_()
-        t2 = time.perf_counter()
-        run_frames(10, n_sec)
-        torch.cuda.synchronize()
-        dt2 = time.perf_counter() - t2
-        inc2 = graphed.finish() if graphed is not None else 0
-    except Exception as e:
-        err2 = repr(e)[:200]
-    poses, tr, pose_t, tr_t = keep
-    # (collectives outside the try: every rank takes part whether or not its own secondary run succeeded)
-    failed = max_over_ranks(1.0 if err2 else 0.0)
-    dt2 = max_over_ranks(dt2)
-    if failed or dt2 <= 0:
-        proc_track = {"error": err2 or "failed on another rank"}
-    else:
-        proc_track = {"frames_per_s": n_sec * world_size / dt2, "frames": n_sec, "samples_per_ray": float(cnt_sum.sum().item()) / n_sec,
-                      "alpha_coverage": float(cov_sum.sum().item()) / n_sec, "frames_incomplete_in_graph": int(inc2) - int(incomplete),
-                      "what": "synthetic.procedural_pose_track(200), the workload of the round-1/2 bench lines"}
+    proc_track = None
+    if args.full:
+        dt2, err2, inc2 = 0.0, None, 0
+        n_sec = min(max(args.steps, 20), 100)
+        keep = (poses, tr, pose_t, tr_t)
+        try:
+            poses, tr = syn.procedural_pose_track(200)
+            pose_t, tr_t = torch.as_tensor(poses, device=dev), torch.as_tensor(tr, device=dev)
+            run_frames(0, 10)
+            torch.cuda.synchronize()
+            stat_acc.zero_()
+            t2 = time.perf_counter()
+            run_frames(10, n_sec)
+            torch.cuda.synchronize()
+            dt2 = time.perf_counter() - t2
+            inc2 = graphed.finish() if graphed is not None else 0
+        except Exception as e:
+            err2 = repr(e)[:200]
+        poses, tr, pose_t, tr_t = keep
+        # (collectives outside the try: every rank takes part whether or not its own secondary run succeeded)
+        failed = max_over_ranks(1.0 if err2 else 0.0)
+        dt2 = max_over_ranks(dt2)
+        if failed or dt2 <= 0:
+            proc_track = {"error": err2 or "failed on another rank"}
+        else:
+            proc_track = {"frames_per_s": n_sec * world_size / dt2, "frames": n_sec, "samples_per_ray": float(cnt_sum.sum().item()) / n_sec,
+                          "alpha_coverage": float(cov_sum.sum().item()) / n_sec, "frames_incomplete_in_graph": int(inc2) - int(incomplete),
+                          "what": "synthetic.procedural_pose_track(200), the workload of the round-1/2 bench lines"}
     # per-kernel timing for the roofline block: HIP events around every launch of the two dominant
     # stages on the stream they run on.  Recording ~50 events per frame costs ~10 % of the frame,
     # so `value` comes from the un-instrumented pass above and the SAME K frames are then launched
     # once more with the events enabled (`ms_per_step_instrumented`).
-    prof = not args.no_profile
+    prof = args.full and not args.no_profile
     dt_prof = None
     if prof:
         _lib.check(L.ia_profile_enable(1))
@@ -1131,16 +1152,17 @@ def main():
         "frames_per_rank": frames_per_rank,
         "samples_per_ray": main_samples_per_ray,
         "alpha_coverage": main_alpha_coverage,
-        "procedural_track": proc_track,
         "frames_in_flight": (args.in_flight if graphed is not None else 1),
-        "one_frame_in_flight": ({"frames_per_s": one_fps * world_size, "frame_latency_ms": 1e3 / one_fps} if one_fps else None),
         "render_loop_iters": model.renderer.last_iters, "launch_mode": mode,
         "spinup_ms": spinup_ms, "spinup_windows": len(windows),
         "value_first_window": windows[0] * world_size, "value_steady": float(np.mean(windows[-3:])) * world_size,
         "frames_rerendered_eagerly": int(incomplete),
-        "ms_per_step_instrumented": (dt_prof / args.steps * 1e3) if dt_prof else None,
-        "dump_outputs": dumped,
+        "dump_outputs": dumped, "full": args.full,
     }
+    if args.full:   # (a plain run's line carries none of these keys, nor roofline / hashgrid_lookup / mfma / train / cpu_baseline)
+        result.update(procedural_track=proc_track,
+                      one_frame_in_flight=({"frames_per_s": one_fps * world_size, "frame_latency_ms": 1e3 / one_fps} if one_fps else None),
+                      ms_per_step_instrumented=(dt_prof / args.steps * 1e3) if dt_prof else None)
     result["ranks"] = rank_report(rank, world_size, dev, {"frames_timed": int(timed_frames), "frames_per_s_local_clock": timed_frames / dt_local,
                                                            "launch_mode": mode, "frames_in_flight": (args.in_flight if graphed is not None else 1)})
     if roof is not None:

@@ -88,6 +88,30 @@ def test_bench_quotes_a_counter_summary_only_for_the_device_code_it_runs(tmp_pat
     assert j is None and "no PMC summary" in src
 
 
+def test_bench_keeps_everything_but_the_headline_behind_full(monkeypatch, capsys):
+    """`--train-steps` / `--cpu-frames` size legs of the `--full` run: a plain run has none (asking for one is an error, not a
+    silent no-op), `--full` has the defaults a run without options had before the option existed."""
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert (a.full, a.train_steps, a.cpu_frames) == (False, 0, 0)
+    a = parse("--cpu-frames", "0", "--train-steps", "0", "--no-profile")
+    assert (a.full, a.train_steps, a.cpu_frames) == (False, 0, 0)
+    a = parse("--full")
+    assert (a.full, a.train_steps, a.cpu_frames, a.no_profile) == (True, 100, 3, False)
+    a = parse("--full", "--gpus", "2")
+    assert (a.train_steps, a.cpu_frames) == (0, 3)
+    a = parse("--full", "--train-steps", "12", "--cpu-frames", "0")
+    assert (a.train_steps, a.cpu_frames) == (12, 0)
+    for argv in (("--train-steps", "12"), ("--cpu-frames", "3")):
+        with pytest.raises(SystemExit):
+            parse(*argv)
+        assert "--full" in capsys.readouterr().err
+
+
 def test_ensure_current_rebuilds_a_stale_library_and_only_then(tmp_path, monkeypatch):
     """`build.ensure_current()` (called by conftest, bench.py and __graft_entry__.smoke before anything loads the library): nothing
     happens for a current library or while an A/B variant is run on purpose; a library that does not match the checkout is rebuilt

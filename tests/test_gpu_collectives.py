@@ -130,7 +130,7 @@ def test_bench_two_ranks_share_the_one_gpu(mode):
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["IA_BENCH_SHARE_DEVICE"] = "1"
-    extra = {"render": ["--train-steps", "12"], "train": ["--train-only"], "tile": ["--tile-shard"], "train-hang": ["--train-only"]}[mode]
+    extra = {"render": ["--full", "--train-steps", "12"], "train": ["--train-only"], "tile": ["--tile-shard"], "train-hang": ["--train-only"]}[mode]
     if mode == "train-hang":
         env.update(IA_TEST_CHILD_HANG_RANK="1", IA_BENCH_CHILD_TIMEOUT="70")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "3", "--cpu-frames", "0",

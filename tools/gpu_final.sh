@@ -4,12 +4,12 @@
 #   -> training kernel stats.   usage (through gpurun): bash tools/gpu_final.sh r05
 R=${GRAFT_REPO_ROOT:-.}; O=$R/gpurun_out; mkdir -p $O; cd $R
 RND=${1:-r05}
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/${RND}_bench_driver.json 2> $O/${RND}_bench_driver.err
+( time python bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/${RND}_bench_driver.json 2> $O/${RND}_bench_driver.err
 tail -3 $O/${RND}_bench_driver.err
-( time python bench.py ) > $O/${RND}_bench_default.json 2> $O/${RND}_bench_default.err
+( time python bench.py --full ) > $O/${RND}_bench_default.json 2> $O/${RND}_bench_default.err
 tail -3 $O/${RND}_bench_default.err
 cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/pp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o r -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --cpu-frames 0 > $O/${RND}_bench_prof.json 2> $O/${RND}_bench_prof.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o r -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-frames 0 > $O/${RND}_bench_prof.json 2> $O/${RND}_bench_prof.err
 cp /tmp/pp/r_kernel_stats.csv $O/${RND}_bench_kernel_stats.csv 2>/dev/null; head -6 $O/${RND}_bench_kernel_stats.csv | cut -c1-120
 cd $R; bash tools/prof_train_stats.sh 2>&1 | tail -12
 python - <<PY

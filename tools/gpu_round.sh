@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-.}; O=$R/gpurun_out; mkdir -p $O; cd $R
 tag=${1:-x}
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_ref_pin.py tests/test_gpu_fullconfig.py tests/test_gpu_edge_cases.py -x -q -m gpu > $O/t_${tag}.log 2>&1
 tail -5 $O/t_${tag}.log | cut -c1-300
-timeout 300 python bench.py --cpu-frames 0 --train-steps 0 > $O/bench_${tag}.json 2> $O/bench_${tag}.err
+timeout 300 python bench.py --full --cpu-frames 0 --train-steps 0 > $O/bench_${tag}.json 2> $O/bench_${tag}.err
 python - <<PY
 import json
 try:

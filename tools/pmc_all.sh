@@ -10,7 +10,7 @@ run() {  # run <dir> <counter set> -- <command...>
   timeout 240 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/$d -o r -- "$@" > $O/$d.log 2>&1
   echo "$d rc=$? $(ls $O/$d 2>/dev/null | tr '\n' ' ')"
 }
-BENCH="python $R/bench.py --steps 3 --warmup 2 --cpu-frames 0 --train-steps 20 --no-graph --no-profile --spinup-max-ms 50"
+BENCH="python $R/bench.py --full --steps 3 --warmup 2 --cpu-frames 0 --train-steps 20 --no-graph --no-profile --spinup-max-ms 50"
 for c in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" \
          "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" "TCC_HIT_sum TCC_MISS_sum" \
          "TCP_PENDING_STALL_CYCLES_sum TCP_TA_TCP_STATE_READ_sum" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES" \

@@ -2,7 +2,7 @@
 # dev tool: kernel trace of a training-only bench run -> per-step breakdown
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; rm -rf $O/prof_train
-timeout 200 rocprofv3 --kernel-trace --output-format csv -d $O/prof_train -o r -- python $R/bench.py --steps 2 --warmup 1 --cpu-frames 0 --train-steps 40 > $O/prof_train.log 2>&1
+timeout 200 rocprofv3 --kernel-trace --output-format csv -d $O/prof_train -o r -- python $R/bench.py --full --steps 2 --warmup 1 --cpu-frames 0 --train-steps 40 > $O/prof_train.log 2>&1
 python - <<'PY'
 import csv, collections, os, glob
 f=glob.glob(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/prof_train/**/*kernel_trace.csv", recursive=True)[0]
