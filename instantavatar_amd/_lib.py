@@ -1,10 +1,15 @@
 """ctypes binding of libinstantavatar_hip.so (the C ABI in include/instantavatar_hip.h).
 
 There is NO fallback: if the library is missing or a call fails, this raises.
-Tensors are passed as raw device pointers + the current HIP stream.
+The header is the single source of the binding: `lib()` parses its prototypes (`parse_header`) and sets every function's
+restype / argtypes from them, and `call(name, *args)` -- the one way the package launches a kernel -- marshals its
+arguments against the same record: tensors as raw device pointers (checked: on the GPU, contiguous, of the dtype the
+pointee type admits), descriptor structs by reference, the current HIP stream when the caller leaves it out.
 """
+import collections
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -49,118 +54,89 @@ class SmplBody(C.Structure):
     _fields_ = [("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p), ("lbs_weights", C.c_void_p),
                 ("J0", C.c_void_p), ("JS", C.c_void_p), ("parents", C.c_void_p), ("n_verts", C.c_int)]
 
-_lib = None
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip.h")
 
-_VP = C.c_void_p
-_SIGS = {
-    "ia_version": (C.c_int, []),
-    "ia_last_error": (C.c_char_p, []),
-    "ia_source_manifest": (C.c_char_p, []),
-    "ia_hash_desc_init": (C.c_int, [C.POINTER(HashDesc), C.c_int, C.c_int, C.c_int, C.c_float]),
-    "ia_smpl_tfs": (C.c_int, [_VP] * 8 + [_VP]),
-    "ia_smpl_tfs_bwd": (C.c_int, [_VP] * 9),
-    "ia_voxelise_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "ia_voxelise_weights": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_size_t, _VP]),
-    "ia_precompute": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.POINTER(SnarfGrid), _VP]),
-    "ia_precompute_workspace_bytes": (C.c_size_t, [C.POINTER(SnarfGrid)]),
-    "ia_precompute_ws": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.POINTER(SnarfGrid), _VP, C.c_size_t, _VP]),
-    "ia_snarf_search": (C.c_int, [_VP, C.c_int, _VP, _VP, C.POINTER(C.c_int32), C.c_int, C.POINTER(SnarfGrid),
-                                  C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP]),
-    "ia_snarf_search_compact": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int,
-                                          C.POINTER(SnarfGrid), C.c_float, C.c_float, _VP, C.c_int32, _VP, _VP,
-                                          _VP, C.c_int, _VP]),
-    "ia_snarf_search_jinv_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "ia_snarf_search_compact_jinv": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int,
-                                               C.POINTER(SnarfGrid), C.c_float, C.c_float, _VP, _VP, C.c_int32, _VP, _VP,
-                                               _VP, C.c_int, _VP, C.c_size_t, _VP]),
-    "ia_field_fwd": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(Field), _VP, _VP, _VP]),
-    "ia_field_act_stride": (C.c_int, [C.c_int]),
-    "ia_field_fwd_train": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(Field), _VP, _VP, _VP, _VP]),
-    "ia_hashgrid_bwd": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(Field), _VP, _VP, _VP, _VP]),
-    "ia_hashgrid_bwd_levels": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(Field), _VP, _VP, C.c_int, C.c_int, _VP]),
-    "ia_candidate_gather_fwd": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_float, _VP, _VP, _VP]),
-    "ia_candidate_gather_bwd": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, _VP]),
-    "ia_mesh_signed_distance": (C.c_int, [_VP, C.c_long, _VP, _VP, C.c_int, _VP, _VP]),
-    "ia_grid_cell_centres": (C.c_int, [C.c_int, _VP, _VP, _VP]),
-    "ia_make_rays": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, _VP, _VP, _VP]),
-    "ia_mask_edge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "ia_mask_edge": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_size_t, _VP]),
-    "ia_mask_dilate": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_size_t, _VP]),
-    "ia_nonzero_select_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "ia_nonzero_select": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, _VP,
-                                    _VP, C.c_size_t, _VP]),
-    "ia_patch_corners": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP]),
-    "ia_near_far": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
-    "ia_edge_indices": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP]),
-    "ia_sample_batch": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP,
-                                  _VP, _VP, _VP, _VP, _VP]),
-    "ia_field_frags_bytes": (C.c_size_t, []),
-    "ia_field_prepare": (C.c_int, [C.POINTER(Field), _VP, _VP]),
-    "ia_smpl_nn_deform": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP]),
-    "ia_smpl_query_workspace_bytes": (C.c_size_t, [C.c_int]),
-    "ia_smpl_deform_query": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_float, C.POINTER(Field), C.c_float,
-                                       C.c_int, _VP, _VP, _VP, C.c_size_t, _VP, _VP]),
-    "ia_smpl_nn_grid_bytes": (C.c_size_t, [C.c_int]),
-    "ia_smpl_nn_grid_build": (C.c_int, [_VP, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
-    "ia_snarf_implicit_bwd_workspace_bytes": (C.c_size_t, [C.c_long]),
-    "ia_snarf_implicit_bwd": (C.c_int, [_VP, _VP, _VP, _VP, C.c_long, _VP, C.POINTER(SnarfGrid), _VP, _VP, C.c_size_t, _VP]),
-    "ia_snarf_implicit_bwd_compact": (C.c_int, [_VP, _VP, _VP, C.c_long, _VP, _VP, C.c_int, C.POINTER(SnarfGrid), _VP, _VP, C.c_size_t, _VP]),
-    "ia_snarf_inverse_skinning": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_long, _VP, _VP, C.c_int, C.POINTER(SnarfGrid), _VP, _VP, _VP]),
-    "ia_snarf_inverse_skinning_bwd": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_long, _VP, _VP, C.c_int, C.POINTER(SnarfGrid), _VP, _VP,
-                                                _VP, _VP, C.c_size_t, _VP]),
-    "ia_expand_candidate_points": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP]),
-    "ia_nerf_loss": (C.c_int, [_VP] * 5 + [C.c_int, C.c_longlong, C.c_float, C.c_float, C.c_float] + [_VP, _VP, C.c_int] + [_VP] * 5),
-    "ia_field_grad_scale": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP]),
-    "ia_field_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "ia_field_bwd": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, _VP, C.POINTER(Field)] + [_VP] * 7 + [C.c_size_t, _VP]),
-    "ia_hashgrid_fwd": (C.c_int, [_VP, C.c_int, C.POINTER(Field), _VP, _VP]),
-    "ia_hashgrid_fwd_planes": (C.c_int, [_VP, C.c_int, C.POINTER(Field), _VP, C.c_size_t, _VP]),
-    "ia_candidate_max": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_float, C.c_int, _VP, _VP, _VP]),
-    "ia_raymarch_test": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, _VP, C.POINTER(OccGrid), _VP, C.c_int,
-                                   _VP, _VP, _VP, _VP]),
-    "ia_composite_test": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_float, _VP]),
-    "ia_raymarch_train": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, C.POINTER(OccGrid), _VP, C.c_int, _VP, _VP]),
-    "ia_occupancy_workspace_bytes": (C.c_size_t, [C.c_int]),
-    "ia_occupancy_from_density": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP]),
-    "ia_occupancy_pack": (C.c_int, [_VP, C.c_int, _VP, _VP]),
-    "ia_query_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "ia_deform_query": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int,
-                                  C.POINTER(SnarfGrid), C.POINTER(Field), _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
-    "ia_density_init_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "ia_density_init_workspace_bytes_batched": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "ia_density_grid_init": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, C.POINTER(C.c_int32), C.c_int,
-                                       C.POINTER(SnarfGrid), C.POINTER(Field), _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
-    "ia_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "ia_render_test": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP,
-                                 C.POINTER(C.c_int32), C.c_int, C.POINTER(SnarfGrid), C.POINTER(Field), C.c_int,
-                                 C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
-    "ia_transform_rays_w2s": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP, _VP]),
-    "ia_march_train_compact": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, C.POINTER(OccGrid), C.c_int, _VP, _VP, _VP,
-                                         _VP, _VP, _VP, _VP, C.c_int, _VP]),
-    "ia_composite_train_fwd": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP,
-                                         C.c_float, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "ia_composite_train_bwd": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP,
-                                         _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "ia_candidate_argmax": (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
-    "ia_profile_enable": (C.c_int, [C.c_int]),
-    "ia_profile_reset": (C.c_int, []),
-    "ia_profile_get": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
-    "ia_profile_get_units": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int]),
-    "ia_search_kernel_info": (C.c_int, [C.POINTER(C.c_int)] * 4),
-    "ia_frame_stats": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP]),
-    "ia_pack_rgba8": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP]),
-    "ia_smpl_nn_compact": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "ia_smpl_nn_compact_bwd": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP]),
-    "ia_ray_samples_bwd": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP]),
-    "ia_smpl_lbs_workspace_bytes": (C.c_size_t, [C.c_int]),
-    "ia_smpl_lbs_fwd": (C.c_int, [C.POINTER(SmplBody)] + [_VP] * 9 + [_VP, C.c_size_t, _VP]),
-    "ia_smpl_lbs_bwd": (C.c_int, [C.POINTER(SmplBody)] + [_VP] * 10 + [_VP, C.c_size_t, _VP]),
-    "ia_adam_workspace_bytes": (C.c_size_t, []),
-    "ia_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int, _VP, _VP, C.c_int, _VP, C.c_size_t, _VP]),
-    "ia_selftest_shared_rcp": (C.c_int, [_VP, _VP, C.c_int, _VP, _VP, _VP]),
-    "ia_selftest_jinv_update": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP]),
-}
-EXPORTED = sorted(_SIGS)
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
+            "long long": C.c_longlong, "int32_t": C.c_int32}
+_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
+_STRUCTS = {"ia_snarf_grid": SnarfGrid, "ia_hash_desc": HashDesc, "ia_field": Field, "ia_occ_grid": OccGrid,
+            "ia_adam_tensor": AdamTensor, "ia_smpl_body": SmplBody}
+# Pointee type -> the dtypes a tensor handed to `call` for such a parameter may have (None: any), fixed from what the call
+# sites pass.  Every pointer to a scalar binds as c_void_p (device tensors and host arrays alike); the pointee only feeds this check.
+#   uint8_t   uint8, and bool: the one parameter kind that legitimately receives two dtypes -- DensityGrid's occ_bool outputs are
+#             bool tensors whose bytes 0 / 1 the kernels write
+#   uint16_t  float16: the header's fp16 convention
+#   uint32_t  int32: the occupancy bits, the encoder planes and the grad-scale state are allocated as int32 words
+#   double, int, uint64_t  no tensor at all: HOST arrays (ia_make_rays, the profile getters), given as ctypes objects
+_POINTEES = {"float": (torch.float32,), "int32_t": (torch.int32,), "int64_t": (torch.int64,), "long long": (torch.int64,),
+             "uint8_t": (torch.uint8, torch.bool), "uint16_t": (torch.float16,), "uint32_t": (torch.int32,), "void": None,
+             "double": (), "int": (), "uint64_t": ()}
+
+#: one parameter of a prototype.  kind: "scalar" | "pointer" (to a scalar or void; `of` = admitted dtypes) |
+#: "struct" (`of` = the ctypes mirror) | "str"
+Param = collections.namedtuple("Param", "name ctype kind of")
+Decl = collections.namedtuple("Decl", "restype params stream")   # stream: the last parameter is `void *stream`
+
+
+def parse_header(text):
+    """{function name: Decl} of every prototype in the text of include/instantavatar_hip.h.  Not a C parser: the header
+    holds comments, preprocessor lines, `typedef struct {...} name;` and `ret name(type [*]param, ...);` over the types of
+    the tables above, and anything else -- a type that is not in them, a function pointer, an array parameter -- raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+\w*\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    text = re.sub(r'extern\s+"C"\s*\{|\}', " ", text)
+    decls = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"(int|size_t|const char \*) ?(\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise ImportError("instantavatar_hip.h: cannot parse the declaration `%s`" % stmt)
+        ret, fname, arglist = m.groups()
+        params = []
+        for arg in ([] if arglist.strip() in ("", "void") else arglist.split(",")):
+            a = re.fullmatch(r"\s*(const )?([\w ]+?) ?(\*?) ?(\w+)\s*", arg)
+            const, base, star, pname = a.groups() if a else (None, None, None, None)
+            if not star and base in _SCALARS:
+                params.append(Param(pname, _SCALARS[base], "scalar", None))
+            elif star and base in _STRUCTS:
+                params.append(Param(pname, C.POINTER(_STRUCTS[base]), "struct", _STRUCTS[base]))
+            elif star and base in _POINTEES:
+                params.append(Param(pname, C.c_void_p, "pointer", _POINTEES[base]))
+            elif star and const and base == "char":
+                params.append(Param(pname, C.c_char_p, "str", None))
+            else:
+                raise ImportError("instantavatar_hip.h: %s: cannot classify the parameter `%s`" % (fname, arg.strip()))
+        stream = bool(params) and params[-1].name == "stream" and params[-1].of is None and params[-1].kind == "pointer"
+        decls[fname] = Decl(_RETURNS[ret], tuple(params), stream)
+    return decls
+
+
+_decls = None
+
+
+def declarations():
+    """parse_header of this checkout's header, read once."""
+    global _decls
+    if _decls is None:
+        try:
+            with open(HEADER_PATH) as f:
+                text = f.read()
+        except OSError as e:
+            raise ImportError("instantavatar_amd: the C header %s is missing (%s); the binding is derived from it"
+                              % (os.path.normpath(HEADER_PATH), e))
+        _decls = parse_header(text)
+    return _decls
+
+
+def __getattr__(name):
+    if name == "EXPORTED":       # the sorted names of the declared functions
+        return sorted(declarations())
+    raise AttributeError(name)
+
+
+_Tensor, _Structure = torch.Tensor, C.Structure     # (module-level names: `call` looks them up per argument)
+_lib = None
+_bound = {}      # name -> (ctypes function, its pointer parameters, parameter count, ends in `void *stream`, returns int): for `call`
 
 
 def lib():
@@ -189,10 +165,14 @@ def lib():
                     "instantavatar_amd: %s was built from other sources than this checkout (differs in: %s). Rebuild it "
                     "(`python -m instantavatar_amd.build`), or set IA_ALLOW_STALE_LIB=1 to run it anyway." % (LIB_PATH, ", ".join(diff)))
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, d in declarations().items():
             fn = getattr(l, name)  # AttributeError if a symbol is missing
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype = d.restype
+            fn.argtypes = [p.ctype for p in d.params]
+            # what `call` does per pointer parameter: (index, name, admitted dtypes, struct); a struct parameter admits no tensor
+            ptrs = tuple((i, p.name, (), p.of) if p.kind == "struct" else (i, p.name, p.of, None)
+                         for i, p in enumerate(d.params[:-1] if d.stream else d.params) if p.kind in ("pointer", "struct"))
+            _bound[name] = (fn, ptrs, len(d.params), d.stream, d.restype is C.c_int)
         _lib = l
     return _lib
 
@@ -238,6 +218,69 @@ def require_cuda(*ts):
             raise IAError("instantavatar_amd kernels need tensors on the GPU (got %s); there is no CPU path" % t.device)
 
 
+def _reject(name, pname, why):
+    raise IAError("%s: argument `%s` %s" % (name, pname, why))
+
+
+def _reject_tensor(name, pname, t, dtypes, struct):
+    if struct is not None:
+        _reject(name, pname, "is a tensor where a %s is declared" % struct.__name__)
+    if not t.is_cuda:
+        _reject(name, pname, "must be on the GPU (got %s); there is no CPU path" % t.device)
+    if not t.is_contiguous():
+        _reject(name, pname, "must be contiguous (got strides %s for shape %s)" % (tuple(t.stride()), tuple(t.shape)))
+    _reject(name, pname, "is %s where the header admits %s" % (t.dtype, " / ".join(map(str, dtypes)) or "no tensor (a host array)"))
+
+
+def call(name, *args):
+    """Call the C-ABI function `name` with `args` marshalled against its prototype in the header:
+
+      pointer parameter   a tensor (its data_ptr(), after checking that it is on the GPU, contiguous and of a dtype the
+                          pointee admits, see _POINTEES), None (NULL), an int (a raw device address: sub-buffers), a descriptor
+                          struct (passed by reference), or any other ctypes object (host arrays, byref(...)) as it is
+      scalar parameter    a Python number
+      void *stream        may be left out as the last argument: the current stream (`stream()`)
+
+    A wrong argument count or a failed tensor check raises IAError naming the function and the parameter, before
+    anything is launched.  Functions that return a status raise through `check` when it is negative; the others
+    (`*_bytes`, ia_field_act_stride, ia_version) return their value.
+
+    Lifetime: `args` holds every tensor, temporaries included, until the function has returned, i.e. until the launch is
+    enqueued; a block the allocator hands out again after that is reused in stream order behind the kernel, which is
+    safe on the same stream.  (Not so for a temporary given to `ptr()`: it dies before the launch.)"""
+    f = _bound.get(name)
+    if f is None:
+        lib()
+        f = _bound.get(name)
+        if f is None:
+            raise IAError("%s is not declared in include/instantavatar_hip.h" % name)
+    fn, ptrs, n, has_stream, int_ret = f
+    if len(args) != n:
+        if has_stream and len(args) == n - 1:
+            args += (stream(),)
+        else:
+            raise IAError("%s takes %d arguments%s, got %d" % (name, n, " (the trailing stream may be left out)" if has_stream else "", len(args)))
+    if ptrs:
+        out = list(args)
+        for i, pname, dtypes, struct in ptrs:
+            a = out[i]
+            if isinstance(a, _Tensor):
+                if a.is_cuda and a.is_contiguous() and (dtypes is None or a.dtype in dtypes):
+                    out[i] = a.data_ptr()
+                else:
+                    _reject_tensor(name, pname, a, dtypes, struct)
+            elif isinstance(a, _Structure):
+                if type(a) is not struct:
+                    _reject(name, pname, "is a %s where %s is declared" % (type(a).__name__, struct.__name__ if struct else "a pointer to scalars"))
+                out[i] = C.byref(a)
+        rc = fn(*out)
+    else:
+        rc = fn(*args)
+    if int_ret and rc < 0:
+        check(rc, name)
+    return rc
+
+
 def bone_array(bone_ids):
     arr = (C.c_int32 * len(bone_ids))(*[int(b) for b in bone_ids])
     return arr
@@ -271,6 +314,5 @@ def apply_level3_override(hd, n_levels, log2_hashmap_size, level3_res=None):
 
 def make_hash_desc(n_levels=16, log2_hashmap_size=19, base_resolution=16, per_level_scale=1.5, level3_res=None):
     hd = HashDesc()
-    check(lib().ia_hash_desc_init(C.byref(hd), n_levels, log2_hashmap_size, base_resolution, per_level_scale),
-          "ia_hash_desc_init")
+    call("ia_hash_desc_init", hd, n_levels, log2_hashmap_size, base_resolution, per_level_scale)
     return apply_level3_override(hd, n_levels, log2_hashmap_size, level3_res)

@@ -27,7 +27,7 @@ def make_rays(K, c2w, H, W, device):
     d = torch.empty((H, W, 3), device=device)
     dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
     _lib.require_cuda(o)
-    _lib.check(_lib.lib().ia_make_rays(dp(Kinv), dp(R), dp(t), H, W, _lib.ptr(o), _lib.ptr(d), _lib.stream()), "ia_make_rays")
+    _lib.call("ia_make_rays", dp(Kinv), dp(R), dp(t), H, W, o, d)
     return o, d
 
 
@@ -69,7 +69,6 @@ class DeviceFrames:
         """PeopleSnapshotDataset.__getitem__ for split "val" / "test" (peoplesnapshot.py:112-125): the WHOLE frame, white
         background, rays / rgb / alpha flattened to [1, H*W, ...] -- what validation_step hands to render_image_fast."""
         dev = self.images.device
-        L = _lib.lib()
         H, W = self.H, self.W
         n = H * W
         if getattr(self, "_all_pixels", None) is None:
@@ -81,9 +80,8 @@ class DeviceFrames:
         img_u8 = img if img.dtype == torch.uint8 else None
         img_f = None if img_u8 is not None else img.float().contiguous()
         m = self.masks[idx].float().contiguous()
-        _lib.check(L.ia_sample_batch(_lib.ptr(img_u8), _lib.ptr(img_f), _lib.ptr(m), _lib.ptr(self.rays_o), _lib.ptr(self.rays_d), H, W,
-                                     _lib.ptr(self._all_pixels), None, None, 0, 0, n, None, _lib.ptr(rgb), _lib.ptr(alpha), _lib.ptr(ro),
-                                     _lib.ptr(rd), _lib.ptr(bg), None, _lib.stream()), "ia_sample_batch")   # bg NULL = white (:114)
+        _lib.call("ia_sample_batch", img_u8, img_f, m, self.rays_o, self.rays_d, H, W, self._all_pixels, None, None, 0, 0, n, None, rgb,
+                  alpha, ro, rd, bg, None)   # bg NULL = white (:114)
         p = self.smpl_params
         transl = p["transl"][idx]
         near, far = torch.empty(n, device=dev), torch.empty(n, device=dev)
@@ -91,7 +89,7 @@ class DeviceFrames:
             near.fill_(float(self.near))
             far.fill_(float(self.far))
         else:
-            _lib.check(L.ia_near_far(_lib.ptr(transl.contiguous()), n, _lib.ptr(near), _lib.ptr(far), _lib.stream()), "ia_near_far")
+            _lib.call("ia_near_far", transl.contiguous(), n, near, far)
         return {"rgb": rgb[None], "rays_o": ro[None], "rays_d": rd[None], "betas": p["betas"][0][None],
                 "global_orient": p["global_orient"][idx][None], "body_pose": p["body_pose"][idx][None], "transl": transl[None],
                 "alpha": alpha[None], "bg_color": bg.reshape(1, H, W, 3),   # the reference leaves bg_color un-flattened (:114)
@@ -102,7 +100,6 @@ class DeviceFrames:
         out: a batch dict returned by an earlier call (or `training.GraphedTrainStep.inputs`, the static input tensors of
         a captured step): the kernels write into its tensors instead of fresh ones -- no copies afterwards."""
         dev = self.images.device
-        L = _lib.lib()
         H, W = self.H, self.W
         mask2d = self.masks[idx]
         s = self.sampler
@@ -134,9 +131,8 @@ class DeviceFrames:
         img_u8 = img if img.dtype == torch.uint8 else None
         img_f = None if img_u8 is not None else img.float().contiguous()
         m = mask2d.float().contiguous()
-        _lib.check(L.ia_sample_batch(_lib.ptr(img_u8), _lib.ptr(img_f), _lib.ptr(m), _lib.ptr(self.rays_o), _lib.ptr(self.rays_d), H, W,
-                                     _lib.ptr(flat_idx), _lib.ptr(rows), _lib.ptr(cols), n_patch, P, n, _lib.ptr(bg), _lib.ptr(rgb),
-                                     _lib.ptr(alpha), _lib.ptr(ro), _lib.ptr(rd), None, None, _lib.stream()), "ia_sample_batch")
+        _lib.call("ia_sample_batch", img_u8, img_f, m, self.rays_o, self.rays_d, H, W, flat_idx, rows, cols, n_patch, P, n, bg, rgb, alpha,
+                  ro, rd, None, None)
         p = self.smpl_params
         transl = p["transl"][idx]
         near, far = dst("near", n), dst("far", n)
@@ -144,7 +140,7 @@ class DeviceFrames:
             near.fill_(float(self.near))
             far.fill_(float(self.far))
         else:  # distance from the camera to the mid-hip (:146-150), one launch
-            _lib.check(L.ia_near_far(_lib.ptr(transl.contiguous()), n, _lib.ptr(near), _lib.ptr(far), _lib.stream()), "ia_near_far")
+            _lib.call("ia_near_far", transl.contiguous(), n, near, far)
         res = {
             "rgb": rgb.reshape(1, *shape, 3), "rays_o": ro.reshape(1, *shape, 3), "rays_d": rd.reshape(1, *shape, 3),
             "betas": p["betas"][0][None], "global_orient": p["global_orient"][idx][None], "body_pose": p["body_pose"][idx][None],

@@ -11,8 +11,6 @@ here the same operations are C-ABI calls into libinstantavatar_hip.so:
 `voxel_J` lives channel-LAST ([D,H,W,12], one trilinear corner = 48 contiguous
 bytes); `.voxel_J` gives the reference's [1,12,D,H,W] view of the same memory.
 """
-import ctypes as C
-
 import torch
 import torch.nn.functional as F
 
@@ -111,13 +109,11 @@ class ForwardDeformer(torch.nn.Module):
             mk = lambda *s: torch.empty(s, device=tfs.device, dtype=torch.float32)
             fr = self._frame = dict(J=mk(d, h, w, 12), d=mk(1, 3, d, h, w), bbox=mk(6))
             # per-workgroup extrema of the bounding-box reduction (own buffer per deformer replica / stream)
-            fr["ws"] = torch.empty(int(_lib.lib().ia_precompute_workspace_bytes(C.byref(self.grid_desc()))), dtype=torch.uint8,
+            fr["ws"] = torch.empty(int(_lib.call("ia_precompute_workspace_bytes", self.grid_desc())), dtype=torch.uint8,
                                    device=tfs.device)
         tfs_c = tfs.detach().float().contiguous()
-        _lib.check(_lib.lib().ia_precompute_ws(_lib.ptr(self.lbs_voxel_final), _lib.ptr(tfs_c), _lib.ptr(fr["J"]),
-                                               _lib.ptr(fr["d"]) if want_voxel_d else None, _lib.ptr(fr["bbox"]) if want_bbox else None,
-                                               C.byref(self.grid_desc()), _lib.ptr(fr["ws"]), fr["ws"].numel(), _lib.stream()),
-                   "ia_precompute_ws")
+        _lib.call("ia_precompute_ws", self.lbs_voxel_final, tfs_c, fr["J"], fr["d"] if want_voxel_d else None,
+                  fr["bbox"] if want_bbox else None, self.grid_desc(), fr["ws"], fr["ws"].numel())
         # (voxel_d / bbox_deformed None: not computed for this frame -- SNARFDeformer.get_bbox_deformed recomputes on demand)
         self.voxel_J_cl, self.voxel_d, self.bbox_deformed = fr["J"], (fr["d"] if want_voxel_d else None), (fr["bbox"] if want_bbox else None)
 
@@ -134,9 +130,8 @@ class ForwardDeformer(torch.nn.Module):
         xc, valid = mk((1, n, k, 3), torch.float32), mk((1, n, k), torch.uint8)
         J_inv = mk((1, n, k, 3, 3), torch.float32) if want_J_inv else None
         xd_c, tfs_c = xd_tgt.detach().float().contiguous(), tfs.detach().float().contiguous()
-        _lib.check(_lib.lib().ia_snarf_search(_lib.ptr(xd_c), n, _lib.ptr(voxel_J_cl), _lib.ptr(tfs_c), self._bones_c, k,
-                                              C.byref(self.grid_desc()), cvg_thresh, dvg_thresh, _lib.ptr(xc),
-                                              _lib.ptr(valid), None, _lib.ptr(J_inv), _lib.stream()), "ia_snarf_search")
+        _lib.call("ia_snarf_search", xd_c, n, voxel_J_cl, tfs_c, self._bones_c, k, self.grid_desc(), cvg_thresh, dvg_thresh, xc, valid,
+                  None, J_inv)
         return {"result": xc, "valid_ids": valid.bool(), "J_inv": J_inv}
 
     def search(self, xd, cond, tfs, eval_mode=False, want_J_inv=True):
@@ -204,17 +199,14 @@ class _ImplicitDiffFn(torch.autograd.Function):
     def backward(ctx, g):
         xc, J_inv, mask = ctx.saved_tensors
         d = ctx.deformer
-        L = _lib.lib()
         n = mask.numel()
         x = xc.reshape(-1, 3).float().contiguous()
         J = J_inv.reshape(-1, 9).float().contiguous()
         m = mask.reshape(-1).to(torch.uint8).contiguous()
         gg = g.reshape(-1, 3).float().contiguous()
         d_tfs = torch.zeros(ctx.tfs_shape, device=x.device)
-        ws = torch.empty(int(L.ia_snarf_implicit_bwd_workspace_bytes(n)), dtype=torch.uint8, device=x.device)
-        _lib.check(L.ia_snarf_implicit_bwd(_lib.ptr(x), _lib.ptr(J), _lib.ptr(m), _lib.ptr(gg), n,
-                                           _lib.ptr(d.lbs_voxel_final), C.byref(d.grid_desc()), _lib.ptr(d_tfs),
-                                           _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_snarf_implicit_bwd")
+        ws = torch.empty(int(_lib.call("ia_snarf_implicit_bwd_workspace_bytes", n)), dtype=torch.uint8, device=x.device)
+        _lib.call("ia_snarf_implicit_bwd", x, J, m, gg, n, d.lbs_voxel_final, d.grid_desc(), d_tfs, ws, ws.numel())
         return d_tfs, None, None, None, None
 
 
@@ -227,16 +219,14 @@ class _InverseSkinningFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tfs, xc, xd, mask, cand_pt, n_dev, deformer):
-        L = _lib.lib()
         x = xc.reshape(-1, 3).float().contiguous()
         t = xd.reshape(-1, 3).float().contiguous()
         m = mask.reshape(-1).to(torch.uint8).contiguous() if mask is not None else None
         n_init = xc.shape[-2] if mask is not None else 1
         tf = tfs.detach().reshape(-1, 4, 4).float().contiguous()
         out = torch.empty_like(x)
-        _lib.check(L.ia_snarf_inverse_skinning(_lib.ptr(x), _lib.ptr(t), _lib.ptr(cand_pt), n_init, _lib.ptr(m), x.shape[0], _lib.ptr(n_dev),
-                                               _lib.ptr(deformer.lbs_voxel_channel_last()), 1, C.byref(deformer.grid_desc()), _lib.ptr(tf),
-                                               _lib.ptr(out), _lib.stream()), "ia_snarf_inverse_skinning")
+        _lib.call("ia_snarf_inverse_skinning", x, t, cand_pt, n_init, m, x.shape[0], n_dev, deformer.lbs_voxel_channel_last(), 1,
+                  deformer.grid_desc(), tf, out)
         ctx.deformer, ctx.n_init, ctx.tfs_shape, ctx.xd_shape = deformer, n_init, tfs.shape, xd.shape
         ctx.save_for_backward(x, t, m, cand_pt, n_dev, tf)
         return out
@@ -244,15 +234,14 @@ class _InverseSkinningFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, t, m, cand_pt, n_dev, tf = ctx.saved_tensors
-        d, L = ctx.deformer, _lib.lib()
+        d = ctx.deformer
         gg = g.reshape(-1, 3).float().contiguous()
         d_tfs = torch.zeros(ctx.tfs_shape, device=x.device)
         want_dx = ctx.needs_input_grad[2]
         d_e = torch.empty_like(x) if want_dx else None
-        ws = torch.empty(int(L.ia_snarf_implicit_bwd_workspace_bytes(x.shape[0])), dtype=torch.uint8, device=x.device)
-        _lib.check(L.ia_snarf_inverse_skinning_bwd(_lib.ptr(x), _lib.ptr(t), _lib.ptr(cand_pt), ctx.n_init, _lib.ptr(m), _lib.ptr(gg), x.shape[0],
-                                                   _lib.ptr(n_dev), _lib.ptr(d.lbs_voxel_channel_last()), 1, C.byref(d.grid_desc()), _lib.ptr(tf),
-                                                   _lib.ptr(d_tfs), _lib.ptr(d_e), _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_snarf_inverse_skinning_bwd")
+        ws = torch.empty(int(_lib.call("ia_snarf_implicit_bwd_workspace_bytes", x.shape[0])), dtype=torch.uint8, device=x.device)
+        _lib.call("ia_snarf_inverse_skinning_bwd", x, t, cand_pt, ctx.n_init, m, gg, x.shape[0], n_dev, d.lbs_voxel_channel_last(), 1,
+                  d.grid_desc(), tf, d_tfs, d_e, ws, ws.numel())
         d_xd = None
         if want_dx:   # sum the entries of every point: the n_init slots of the dense layout, or the candidates that name the point
             if cand_pt is None:
@@ -277,14 +266,12 @@ class _ImplicitDiffCompactFn(torch.autograd.Function):
     def backward(ctx, g):
         xc, J_inv, n_cand = ctx.saved_tensors
         d = ctx.deformer
-        L = _lib.lib()
         cap = xc.shape[0]
         gg = g.reshape(-1, 3).float().contiguous()
         d_tfs = torch.zeros(ctx.tfs_shape, device=xc.device)
-        ws = torch.empty(int(L.ia_snarf_implicit_bwd_workspace_bytes(cap)), dtype=torch.uint8, device=xc.device)
-        _lib.check(L.ia_snarf_implicit_bwd_compact(_lib.ptr(xc), _lib.ptr(J_inv), _lib.ptr(gg), cap, _lib.ptr(n_cand),
-                                                   _lib.ptr(d.lbs_voxel_channel_last()), 1, C.byref(d.grid_desc()), _lib.ptr(d_tfs),
-                                                   _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_snarf_implicit_bwd_compact")
+        ws = torch.empty(int(_lib.call("ia_snarf_implicit_bwd_workspace_bytes", cap)), dtype=torch.uint8, device=xc.device)
+        _lib.call("ia_snarf_implicit_bwd_compact", xc, J_inv, gg, cap, n_cand, d.lbs_voxel_channel_last(), 1, d.grid_desc(), d_tfs, ws,
+                  ws.numel())
         return d_tfs, None, None, None, None
 
 
@@ -304,10 +291,8 @@ def voxelise_skinning_weights(points, verts, vert_weights, dims):
     CPU tensors raise (the checkers of this kernel live in oracle/ and tests/)."""
     _lib.require_cuda(points)
     d, h, w = dims
-    L = _lib.lib()
     pts, vs, vw = points.float().contiguous(), verts.float().contiguous(), vert_weights.float().contiguous()
     out = torch.empty((24, d, h, w), device=points.device)
-    ws = torch.empty(int(L.ia_voxelise_workspace_bytes(d, h, w)), dtype=torch.uint8, device=points.device)
-    _lib.check(L.ia_voxelise_weights(_lib.ptr(pts), _lib.ptr(vs), vs.shape[0], _lib.ptr(vw), d, h, w, SMOOTH_PASSES,
-                                     _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_voxelise_weights")
+    ws = torch.empty(int(_lib.call("ia_voxelise_workspace_bytes", d, h, w)), dtype=torch.uint8, device=points.device)
+    _lib.call("ia_voxelise_weights", pts, vs, vs.shape[0], vw, d, h, w, SMOOTH_PASSES, out, ws, ws.numel())
     return out

@@ -16,8 +16,6 @@ instantavatar_amd NeRFNGPNet, and the reference's masked structure for any other
 Only k = 1 is supported (the reference squeezes the neighbour axis: "we use the nearest neighbor
 only", smpl_deformer.py:98-100).
 """
-import ctypes as C
-
 import torch
 
 from .. import _lib
@@ -41,16 +39,14 @@ class _SmplLbsFn(torch.autograd.Function):
         body, keep = smpl.lbs_constants()
         dev = keep["v_template"].device
         V = body.n_verts
-        L = _lib.lib()
         b = betas.detach().reshape(-1)[:10].float().contiguous()
         pose = torch.cat([global_orient.detach().reshape(3), body_pose.detach().reshape(69)]).float().contiguous()
         tr = transl.detach().reshape(3).float().contiguous() if transl is not None else None
         pose_t, po_t = deformer._template_constants(dev)
-        ws = _lib.scratch(deformer, "_lbs_ws", L.ia_smpl_lbs_workspace_bytes(V), dev)
+        ws = _lib.scratch(deformer, "_lbs_ws", _lib.call("ia_smpl_lbs_workspace_bytes", V), dev)
         T_inv, verts = torch.empty((1, V, 4, 4), device=dev), torch.empty((1, V, 3), device=dev)
         verts_t, w2s = torch.empty((1, V, 3), device=dev), torch.empty((1, 4, 4), device=dev)
-        _lib.check(L.ia_smpl_lbs_fwd(C.byref(body), _lib.ptr(b), _lib.ptr(pose), _lib.ptr(tr), _lib.ptr(pose_t), _lib.ptr(po_t), _lib.ptr(T_inv),
-                                     _lib.ptr(verts), _lib.ptr(verts_t), _lib.ptr(w2s), _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_smpl_lbs_fwd")
+        _lib.call("ia_smpl_lbs_fwd", body, b, pose, tr, pose_t, po_t, T_inv, verts, verts_t, w2s, ws, ws.numel())
         ctx.deformer = deformer
         ctx.shapes = (betas.shape, body_pose.shape, global_orient.shape, None if transl is None else transl.shape)
         ctx.save_for_backward(b, pose, tr if tr is not None else torch.empty(0, device=dev))
@@ -66,18 +62,15 @@ class _SmplLbsFn(torch.autograd.Function):
         body, keep = d.body_model.lbs_constants()
         dev = b.device
         V = body.n_verts
-        L = _lib.lib()
         s_b, s_bp, s_go, s_tr = ctx.shapes
         if d_T_inv is None and d_w2s is None:
             return None, None, None, None, None
         g = d_T_inv.reshape(V, 4, 4).float().contiguous() if d_T_inv is not None else torch.zeros((V, 4, 4), device=dev)
         gw = d_w2s.reshape(4, 4).float().contiguous() if d_w2s is not None else None
         pose_t, po_t = d._template_constants(dev)
-        ws = _lib.scratch(d, "_lbs_ws", L.ia_smpl_lbs_workspace_bytes(V), dev)
+        ws = _lib.scratch(d, "_lbs_ws", _lib.call("ia_smpl_lbs_workspace_bytes", V), dev)
         d_b, d_pose, d_tr = torch.empty(10, device=dev), torch.empty(72, device=dev), torch.empty(3, device=dev)
-        _lib.check(L.ia_smpl_lbs_bwd(C.byref(body), _lib.ptr(b), _lib.ptr(pose), _lib.ptr(tr) if ctx.has_tr else None, _lib.ptr(pose_t), _lib.ptr(po_t),
-                                     _lib.ptr(g), _lib.ptr(gw), _lib.ptr(d_b), _lib.ptr(d_pose), _lib.ptr(d_tr), _lib.ptr(ws), ws.numel(),
-                                     _lib.stream()), "ia_smpl_lbs_bwd")
+        _lib.call("ia_smpl_lbs_bwd", body, b, pose, tr if ctx.has_tr else None, pose_t, po_t, g, gw, d_b, d_pose, d_tr, ws, ws.numel())
         gb = torch.zeros(s_b, device=dev)
         gb.reshape(-1)[:10] = d_b      # (betas [1,10]: the row in use)
         return gb, d_pose[3:].reshape(s_bp), d_pose[:3].reshape(s_go), (d_tr.reshape(s_tr) if ctx.has_tr else None), None
@@ -191,11 +184,10 @@ class SMPLDeformer():
         self._nn_grid_ok = False
         if not (self.use_nn_grid and torch.is_tensor(self.vertices) and self.vertices.is_cuda and self.vertices.shape[0] == 1):
             return
-        L = _lib.lib()
         V = self.vertices.shape[1]
-        buf = _lib.scratch(self, "_nn_grid_buf", L.ia_smpl_nn_grid_bytes(V), self.vertices.device)
+        buf = _lib.scratch(self, "_nn_grid_buf", _lib.call("ia_smpl_nn_grid_bytes", V), self.vertices.device)
         v = self.vertices.detach()
-        _lib.check(L.ia_smpl_nn_grid_build(_lib.ptr(v), V, float(self.threshold), _lib.ptr(buf), buf.numel(), _lib.stream()), "ia_smpl_nn_grid_build")
+        _lib.call("ia_smpl_nn_grid_build", v, V, float(self.threshold), buf, buf.numel())
         self._nn_grid_ok = True
         self._nn_grid_key = (self.vertices.data_ptr(), self.vertices._version, float(self.threshold))
 
@@ -206,7 +198,7 @@ class SMPLDeformer():
         v = self.vertices     # (somebody replaced or rewrote the vertices, or changed the threshold, after prepare_deformer: brute force)
         if self._nn_grid_key != (v.data_ptr(), v._version, float(self.threshold)):
             return None
-        return _lib.ptr(self._nn_grid_buf)
+        return self._nn_grid_buf.data_ptr()     # (a raw address for `call`: the buffer lives on the deformer)
 
     def release_graph(self):
         """drop the autograd graph held by the per-frame attributes (see SNARFDeformer.release_graph)"""
@@ -237,9 +229,8 @@ class SMPLDeformer():
         need_grad = torch.is_grad_enabled() and (self.T_inv.requires_grad or pts.requires_grad)
         idx = torch.empty(P, dtype=torch.int32, device=x.device) if need_grad else None
         if P:
-            _lib.check(_lib.lib().ia_smpl_nn_deform(_lib.ptr(x), P, None, _lib.ptr(self.vertices.detach()), _lib.ptr(self.T_inv.detach()),
-                                                    self.vertices.shape[1], float(self.threshold), _lib.ptr(cano),
-                                                    _lib.ptr(valid), _lib.ptr(idx), _lib.stream()), "ia_smpl_nn_deform")
+            _lib.call("ia_smpl_nn_deform", x, P, None, self.vertices.detach(), self.T_inv.detach(), self.vertices.shape[1],
+                      float(self.threshold), cano, valid, idx)
         if need_grad and P:
             # SMPL refinement with this deformer (SNARF_NGP_refine + deformer=smpl): the reference's pts_cano
             # (smpl_deformer.py:100-107) is differentiable w.r.t. the per-vertex transforms; the nearest-vertex
@@ -264,12 +255,9 @@ class SMPLDeformer():
         sigma = torch.full((P,), float(fill), device=x.device)
         if P == 0:
             return rgb, sigma
-        L = _lib.lib()
-        ws = self._workspace(L.ia_smpl_query_workspace_bytes(P), x.device)
-        _lib.check(L.ia_smpl_deform_query(_lib.ptr(x), P, None, _lib.ptr(self.vertices), _lib.ptr(self.T_inv),
-                                          self.vertices.shape[1], float(self.threshold), C.byref(net.field_desc(P)),
-                                          float(fill), int(nan_to_num), _lib.ptr(rgb), _lib.ptr(sigma), _lib.ptr(ws),
-                                          ws.numel(), self.nn_grid_ptr(), _lib.stream()), "ia_smpl_deform_query")
+        ws = self._workspace(_lib.call("ia_smpl_query_workspace_bytes", P), x.device)
+        _lib.call("ia_smpl_deform_query", x, P, None, self.vertices, self.T_inv, self.vertices.shape[1], float(self.threshold),
+                  net.field_desc(P), float(fill), int(nan_to_num), rgb, sigma, ws, ws.numel(), self.nn_grid_ptr())
         return rgb, sigma
 
     @staticmethod

@@ -14,7 +14,6 @@ field query `deformer(pts, net)` is the fused `ia_deform_query` when `net` is
 an instantavatar_amd NeRFNGPNet, and the generic masked path (reference
 structure, snarf_deformer.py:127-159) for any other callable.
 """
-import ctypes as C
 import os
 
 import torch
@@ -83,8 +82,7 @@ class _CandidateGatherFn(torch.autograd.Function):
         P = arg.shape[0]
         rgb = torch.empty((P, 3), device=arg.device)
         sigma = torch.empty(P, device=arg.device)
-        _lib.check(_lib.lib().ia_candidate_gather_fwd(_lib.ptr(cand_rgb), _lib.ptr(cand_sigma), _lib.ptr(arg), P, float(fill),
-                                                      _lib.ptr(rgb), _lib.ptr(sigma), _lib.stream()), "ia_candidate_gather_fwd")
+        _lib.call("ia_candidate_gather_fwd", cand_rgb, cand_sigma, arg, P, float(fill), rgb, sigma)
         ctx.save_for_backward(arg)
         ctx.n_cand = cand_sigma.shape[0]
         return rgb, sigma
@@ -96,9 +94,7 @@ class _CandidateGatherFn(torch.autograd.Function):
         d_rgb, d_sigma = c(d_rgb), c(d_sigma)
         d_cand_rgb = torch.zeros((ctx.n_cand, 3), device=arg.device)
         d_cand_sigma = torch.zeros(ctx.n_cand, device=arg.device)
-        _lib.check(_lib.lib().ia_candidate_gather_bwd(_lib.ptr(d_rgb), _lib.ptr(d_sigma), _lib.ptr(arg), arg.shape[0],
-                                                      _lib.ptr(d_cand_rgb), _lib.ptr(d_cand_sigma), _lib.stream()),
-                   "ia_candidate_gather_bwd")
+        _lib.call("ia_candidate_gather_bwd", d_rgb, d_sigma, arg, arg.shape[0], d_cand_rgb, d_cand_sigma)
         return d_cand_rgb, d_cand_sigma, None, None
 
 
@@ -113,9 +109,7 @@ class _SmplTfsFn(torch.autograd.Function):
         pose = torch.cat([global_orient.detach().reshape(1, 3), body_pose.detach().reshape(1, 69)], dim=1).float().contiguous()
         trc = transl.detach().reshape(3).float().contiguous()
         tfs, w2s, A = torch.empty_like(fo["tfs"]), torch.empty_like(fo["w2s"]), torch.empty_like(fo["A"])
-        _lib.check(_lib.lib().ia_smpl_tfs(_lib.ptr(deformer._joints_rest), _lib.ptr(deformer._parents32), _lib.ptr(pose),
-                                          _lib.ptr(trc), _lib.ptr(deformer.tfs_inv_t), _lib.ptr(tfs), _lib.ptr(w2s), _lib.ptr(A),
-                                          _lib.stream()), "ia_smpl_tfs")
+        _lib.call("ia_smpl_tfs", deformer._joints_rest, deformer._parents32, pose, trc, deformer.tfs_inv_t, tfs, w2s, A)
         ctx.deformer = deformer
         ctx.shapes = (global_orient.shape, body_pose.shape, transl.shape)
         ctx.save_for_backward(pose, trc)
@@ -129,9 +123,7 @@ class _SmplTfsFn(torch.autograd.Function):
         d_pose = torch.empty(72, device=pose.device)
         d_tr = torch.empty(3, device=pose.device)
         g = d_tfs.reshape(24, 4, 4).float().contiguous()
-        _lib.check(_lib.lib().ia_smpl_tfs_bwd(_lib.ptr(d._joints_rest), _lib.ptr(d._parents32), _lib.ptr(pose), _lib.ptr(trc),
-                                              _lib.ptr(d.tfs_inv_t), _lib.ptr(g), _lib.ptr(d_pose), _lib.ptr(d_tr), _lib.stream()),
-                   "ia_smpl_tfs_bwd")
+        _lib.call("ia_smpl_tfs_bwd", d._joints_rest, d._parents32, pose, trc, d.tfs_inv_t, g, d_pose, d_tr)
         s_go, s_bp, s_tr = ctx.shapes
         return d_pose[:3].reshape(s_go), d_pose[3:].reshape(s_bp), d_tr.reshape(s_tr), None
 
@@ -244,9 +236,7 @@ class SNARFDeformer():
             fo = self._frame_out
             pose = _pose72(go, bp)
             trc = tr.reshape(3).float().contiguous()
-            _lib.check(_lib.lib().ia_smpl_tfs(_lib.ptr(self._joints_rest), _lib.ptr(self._parents32), _lib.ptr(pose),
-                                              _lib.ptr(trc), _lib.ptr(self.tfs_inv_t), _lib.ptr(fo["tfs"]),
-                                              _lib.ptr(fo["w2s"]), _lib.ptr(fo["A"]), _lib.stream()), "ia_smpl_tfs")
+            _lib.call("ia_smpl_tfs", self._joints_rest, self._parents32, pose, trc, self.tfs_inv_t, fo["tfs"], fo["w2s"], fo["A"])
             tfs, w2s, A = fo["tfs"], fo["w2s"], fo["A"]
         self.deformer.precompute(tfs, want_voxel_d=want_bbox, want_bbox=want_bbox)
         self.w2s = w2s
@@ -290,9 +280,7 @@ class SNARFDeformer():
             o2, d2 = torch.empty_like(oc), torch.empty_like(dc)
             near, far = torch.empty(R, device=o.device), torch.empty(R, device=o.device)
             w2s = self.w2s.reshape(4, 4).float().contiguous()
-            _lib.check(_lib.lib().ia_transform_rays_w2s(_lib.ptr(oc), _lib.ptr(dc), _lib.ptr(w2s), R, _lib.ptr(o2),
-                                                        _lib.ptr(d2), _lib.ptr(near), _lib.ptr(far), _lib.stream()),
-                       "ia_transform_rays_w2s")
+            _lib.call("ia_transform_rays_w2s", oc, dc, w2s, R, o2, d2, near, far)
             rays.o, rays.d = o2.reshape(o.shape), d2.reshape(d.shape)
             rays.near, rays.far = near.reshape(o.shape[:-1]), far.reshape(o.shape[:-1])
             return
@@ -346,15 +334,12 @@ class SNARFDeformer():
         pts = pts.reshape(-1, 3).contiguous()
         P = pts.shape[0]
         k = len(self.deformer.init_bones)
-        L = _lib.lib()
-        ws = self._workspace(L.ia_query_workspace_bytes(P, k), pts.device)
+        ws = self._workspace(_lib.call("ia_query_workspace_bytes", P, k), pts.device)
         rgb = torch.empty((P, 3), device=pts.device) if want_rgb else None
         sigma = torch.empty(P, device=pts.device)
         tfs = self.tfs.detach().float().contiguous()
-        _lib.check(L.ia_deform_query(_lib.ptr(pts), P, None, _lib.ptr(self.deformer.voxel_J_cl), _lib.ptr(tfs),
-                                     self.deformer._bones_c, k, C.byref(self.deformer.grid_desc()),
-                                     C.byref(net.field_desc(P * k)), _lib.ptr(rgb), _lib.ptr(sigma), _lib.ptr(dmax),
-                                     _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_deform_query")
+        _lib.call("ia_deform_query", pts, P, None, self.deformer.voxel_J_cl, tfs, self.deformer._bones_c, k, self.deformer.grid_desc(),
+                  net.field_desc(P * k), rgb, sigma, dmax, ws, ws.numel())
         return rgb, sigma
 
     def search_compact(self, pts, n_pts_dev=None, cap=None, want_J_inv=False, n_cand_out=None):
@@ -373,18 +358,16 @@ class SNARFDeformer():
                    n_cand=n_cand_out if n_cand_out is not None else torch.zeros(1, dtype=torch.int32, device=dev),
                    pts=pts, n_pts_dev=n_pts_dev)
         tfs = self.tfs.detach().float().contiguous()
-        L = _lib.lib()
-        head = (_lib.ptr(pts), P, _lib.ptr(n_pts_dev), _lib.ptr(self.deformer.voxel_J_cl), _lib.ptr(tfs),
-                self.deformer._bones_c, k, C.byref(self.deformer.grid_desc()), 1e-5, 1e-1, _lib.ptr(out["cand_xc"]))
-        tail = (cap, _lib.ptr(out["pt_off"]), _lib.ptr(out["pt_cnt"]), _lib.ptr(out["n_cand"]), 0)
+        head = (pts, P, n_pts_dev, self.deformer.voxel_J_cl, tfs, self.deformer._bones_c, k, self.deformer.grid_desc(), 1e-5, 1e-1,
+                out["cand_xc"])
+        tail = (cap, out["pt_off"], out["pt_cnt"], out["n_cand"], 0)
         if want_J_inv:
             out["cand_Jinv"] = torch.empty((cap, 3, 3), device=dev)
             # J_inv of the valid solves before compaction (P x 13 x 36 B)
-            ws = _lib.scratch(self, "_ws_jinv", int(L.ia_snarf_search_jinv_workspace_bytes(P, k)), dev)
-            _lib.check(L.ia_snarf_search_compact_jinv(*head, _lib.ptr(out["cand_Jinv"]), *tail, _lib.ptr(ws), ws.numel(), _lib.stream()),
-                       "ia_snarf_search_compact_jinv")
+            ws = _lib.scratch(self, "_ws_jinv", int(_lib.call("ia_snarf_search_jinv_workspace_bytes", P, k)), dev)
+            _lib.call("ia_snarf_search_compact_jinv", *head, out["cand_Jinv"], *tail, ws, ws.numel())
         else:
-            _lib.check(L.ia_snarf_search_compact(*head, *tail, _lib.stream()), "ia_snarf_search_compact")
+            _lib.call("ia_snarf_search_compact", *head, *tail)
         return out
 
     def candidates_with_grad(self, sc):
@@ -397,8 +380,7 @@ class SNARFDeformer():
             from .fast_snarf.forward_deformer import _InverseSkinningFn
             P = sc["pts"].shape[0]
             cand_pt = torch.empty(sc["cand_xc"].shape[0], dtype=torch.int32, device=sc["pts"].device)
-            _lib.check(_lib.lib().ia_expand_candidate_points(_lib.ptr(sc["pt_off"]), _lib.ptr(sc["pt_cnt"]), P, _lib.ptr(sc["n_pts_dev"]), _lib.ptr(cand_pt),
-                                                             cand_pt.numel(), _lib.stream()), "ia_expand_candidate_points")
+            _lib.call("ia_expand_candidate_points", sc["pt_off"], sc["pt_cnt"], P, sc["n_pts_dev"], cand_pt, cand_pt.numel())
             return _InverseSkinningFn.apply(self.tfs, sc["cand_xc"], sc["pts"], None, cand_pt, sc["n_cand"], self.deformer)
         if "cand_Jinv" not in sc:
             return sc["cand_xc"]
@@ -445,8 +427,7 @@ class SNARFDeformer():
         self._cand_counts.post(sc["n_cand"], cap)
         arg = torch.empty(P, dtype=torch.int32, device=pts.device)
         sig_d = sig_c.detach().float().contiguous()
-        _lib.check(_lib.lib().ia_candidate_argmax(_lib.ptr(sig_d), cap, _lib.ptr(sc["pt_off"]), _lib.ptr(sc["pt_cnt"]), P, k,
-                                                  _lib.ptr(arg), _lib.stream()), "ia_candidate_argmax")
+        _lib.call("ia_candidate_argmax", sig_d, cap, sc["pt_off"], sc["pt_cnt"], P, k, arg)
         return _CandidateGatherFn.apply(rgb_c.float(), sig_c.float(), arg, -1e5)
 
     def deform_train(self, pts, model):

@@ -11,8 +11,6 @@ cross-check of the fused routes in tests/ (test_closure_route_equals_fused_route
 Semantics (what the results must equal): raymarcher_acc.py:83-138 (test loop), :140-186 with :25-36 (training render),
 snarf_deformer.py:127-159 (candidate reduction).  There is no CPU path here either: the tensors must live on the GPU.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -45,7 +43,6 @@ def render_test(renderer, rays, model, bg_color):
     """Test-time wave front around an arbitrary callable.  Per iteration: every alive ray marches N_step =
     clamp(MAX_BATCH_SIZE // alive, 1, MAX_SAMPLES) slots, the callable sees the occupied ones, the compositor folds the
     block into the rays' running colour / depth / transmittance, rays that ran out of slots or of transmittance retire."""
-    L = _lib.lib()
     _lib.require_cuda(rays.o)
     o, d, near, far = _flat_rays(rays)
     near = near.clone()                                           # advanced in place by the marcher
@@ -62,14 +59,11 @@ def render_test(renderer, rays, model, bg_color):
         n_step = max(min(renderer.MAX_BATCH_SIZE // a, S), 1)
         pts = torch.empty((a, n_step, 3), device=dev)
         delta, z = torch.empty((a, n_step), device=dev), torch.empty((a, n_step), device=dev)
-        _lib.check(L.ia_raymarch_test(_lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), _lib.ptr(alive), a, _lib.ptr(grid.occ_bits),
-                                      C.byref(occ), _lib.ptr(step), n_step, _lib.ptr(pts), _lib.ptr(delta), _lib.ptr(z), _lib.stream()),
-                   "ia_raymarch_test")
+        _lib.call("ia_raymarch_test", o, d, near, far, alive, a, grid.occ_bits, occ, step, n_step, pts, delta, z)
         hit = delta > 0
         counter[alive] += hit.sum(dim=-1)
         rgb, sigma = _masked_field(model, pts, hit, 0.0)
-        _lib.check(L.ia_composite_test(_lib.ptr(rgb.contiguous()), _lib.ptr(sigma.contiguous()), _lib.ptr(delta), _lib.ptr(z), _lib.ptr(alive), a,
-                                       n_step, _lib.ptr(color), _lib.ptr(depth), _lib.ptr(trans), 0.01, _lib.stream()), "ia_composite_test")
+        _lib.call("ia_composite_test", rgb.contiguous(), sigma.contiguous(), delta, z, alive, a, n_step, color, depth, trans, 0.01)
         alive = alive[(trans[alive] > 1e-4) & (z[:, -1] > 0)]
         done += n_step
     color = color + trans[:, None] * (bg_color.reshape(-1, 3) if bg_color is not None else 1.0)
@@ -87,7 +81,6 @@ def render_train(renderer, rays, model, noise, bg_color):
     """Training render with MAX_SAMPLES slots per ray (dense): marcher -> jitter -> callable on the occupied slots ->
     (+ sigma noise) -> differentiable compositing in torch ops.  Inside a training step the random draws may be injected
     (`training.StepState.draws`)."""
-    L = _lib.lib()
     _lib.require_cuda(rays.o)
     o, d, near, far = _flat_rays(rays)
     n, S = o.shape[0], renderer.MAX_SAMPLES
@@ -96,8 +89,7 @@ def render_train(renderer, rays, model, noise, bg_color):
     occ = renderer._occ_desc(grid)
     z = torch.empty((n, S), device=o.device)
     with torch.no_grad():
-        _lib.check(L.ia_raymarch_train(_lib.ptr(o.detach()), _lib.ptr(d.detach()), _lib.ptr(near.detach()), _lib.ptr(far.detach()), n,
-                                       _lib.ptr(grid.occ_bits), C.byref(occ), _lib.ptr(step.detach()), S, _lib.ptr(z), _lib.stream()), "ia_raymarch_train")
+        _lib.call("ia_raymarch_train", o.detach(), d.detach(), near.detach(), far.detach(), n, grid.occ_bits, occ, step.detach(), S, z)
     occupied = z > 0
     state = active_step()
     draws = state.draws if state is not None else {}

@@ -140,7 +140,7 @@ def pack_rgba8(out, dst):
     from .. import _lib
     rgb, _, alpha, _ = out
     _lib.require_cuda(rgb, alpha, dst)
-    _lib.check(_lib.lib().ia_pack_rgba8(_lib.ptr(rgb), _lib.ptr(alpha), alpha.numel(), _lib.ptr(dst), _lib.stream()), "ia_pack_rgba8")
+    _lib.call("ia_pack_rgba8", rgb, alpha, alpha.numel(), dst)
 
 
 def fixed_jitter(seed, device, iters=5, G=64):

@@ -12,8 +12,6 @@ tcnn keeps fp32 master parameters and casts them to fp16 on every forward; the
 fp16 shadow here is refreshed only when the master tensor changes
 (`Tensor._version`).
 """
-import ctypes as C
-
 import numpy as np
 import os
 
@@ -228,7 +226,7 @@ class NeRFNGPNet(nn.Module):
                     self._half[0].copy_(self.encoder.params.detach())
                     self._half[1].copy_(self.color_net.params.detach())
             if self._desc is not None and getattr(self, "_frags", None) is not None:
-                _lib.check(_lib.lib().ia_field_prepare(C.byref(self._desc), _lib.ptr(self._frags), _lib.stream()), "ia_field_prepare")
+                _lib.call("ia_field_prepare", self._desc, self._frags)
         self._half_key = key
         self._dirty = False
         return self._half
@@ -308,9 +306,8 @@ class NeRFNGPNet(nn.Module):
             f.col_w3 = c + 2 * (COL_W1 + COL_W2)
             f.mlp_frags = None
             # MFMA weight fragments: rebuilt only when the fp16 shadow changed
-            L = _lib.lib()
-            self._frags = torch.empty(L.ia_field_frags_bytes() // 2, dtype=torch.float16, device=enc.device)
-            _lib.check(L.ia_field_prepare(C.byref(f), _lib.ptr(self._frags), _lib.stream()), "ia_field_prepare")
+            self._frags = torch.empty(_lib.call("ia_field_frags_bytes") // 2, dtype=torch.float16, device=enc.device)
+            _lib.call("ia_field_prepare", f, self._frags)
             f.mlp_frags = self._frags.data_ptr()
             if getattr(self, "_enc_ws_samples", 0):
                 f.enc_ws, f.enc_ws_samples = self._enc_ws.data_ptr(), self._enc_ws_samples
@@ -330,8 +327,7 @@ class NeRFNGPNet(nn.Module):
         V = xc.shape[0]
         rgb = torch.empty((V, 3), device=x.device)
         sigma = torch.empty(V, device=x.device)
-        _lib.check(_lib.lib().ia_field_fwd(_lib.ptr(xc), V, None, C.byref(self.field_desc(V)), _lib.ptr(rgb),
-                                           _lib.ptr(sigma), _lib.stream()), "ia_field_fwd")
+        _lib.call("ia_field_fwd", xc, V, None, self.field_desc(V), rgb, sigma)
         return rgb, sigma
 
     def encode(self, x):
@@ -339,8 +335,7 @@ class NeRFNGPNet(nn.Module):
         _lib.require_cuda(x)
         xc = x.detach().reshape(-1, 3).float().contiguous()
         feat = torch.empty((xc.shape[0], 2 * self.n_levels), device=x.device, dtype=torch.float16)
-        _lib.check(_lib.lib().ia_hashgrid_fwd(_lib.ptr(xc), xc.shape[0], C.byref(self.field_desc()), _lib.ptr(feat),
-                                              _lib.stream()), "ia_hashgrid_fwd")
+        _lib.call("ia_hashgrid_fwd", xc, xc.shape[0], self.field_desc(), feat)
         return feat
 
     def encode_planes(self, x):
@@ -350,6 +345,5 @@ class NeRFNGPNet(nn.Module):
         xc = x.detach().reshape(-1, 3).float().contiguous()
         V = xc.shape[0]
         planes = torch.empty((self.n_levels, V), device=x.device, dtype=torch.int32)
-        _lib.check(_lib.lib().ia_hashgrid_fwd_planes(_lib.ptr(xc), V, C.byref(self.field_desc()), _lib.ptr(planes), V,
-                                                     _lib.stream()), "ia_hashgrid_fwd_planes")
+        _lib.call("ia_hashgrid_fwd_planes", xc, V, self.field_desc(), planes, V)
         return planes

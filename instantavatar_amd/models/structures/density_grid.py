@@ -13,8 +13,6 @@ the bit-packed copy (32 KB) the marcher kernels read, followed by one flag word
 (1 = no border cell occupied, which lets the marcher reject samples outside the aabb
 without a lookup).
 """
-import ctypes as C
-
 import torch
 import torch.nn.functional as F
 
@@ -80,17 +78,14 @@ class DensityGrid(torch.nn.Module):
     def pack_bits(self):
         """refresh occ_bits from density_field (after loading a checkpoint / update)."""
         f8 = self.density_field.to(torch.uint8).contiguous()
-        _lib.check(_lib.lib().ia_occupancy_pack(_lib.ptr(f8), self.grid_size, _lib.ptr(self.occ_bits), _lib.stream()),
-                   "ia_occupancy_pack")
+        _lib.call("ia_occupancy_pack", f8, self.grid_size, self.occ_bits)
 
     def _postprocess(self, density):
         """density [G,G,G] -> density_field + occ_bits (density_grid.py:104-110)."""
         G = self.grid_size
-        L = _lib.lib()
-        ws = self._workspace(L.ia_occupancy_workspace_bytes(G))
+        ws = self._workspace(_lib.call("ia_occupancy_workspace_bytes", G))
         out8 = torch.empty((G, G, G), dtype=torch.bool, device=density.device)   # written as bytes 0 / 1 by the kernel
-        _lib.check(L.ia_occupancy_from_density(_lib.ptr(density.contiguous()), G, _lib.ptr(self.occ_bits), _lib.ptr(out8),
-                                               _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_occupancy_from_density")
+        _lib.call("ia_occupancy_from_density", density.contiguous(), G, self.occ_bits, out8, ws, ws.numel())
         self.density_field = out8
 
     # -- test-time grid (per frame) ----------------------------------------------
@@ -120,25 +115,21 @@ class DensityGrid(torch.nn.Module):
         from ...deformers.snarf_deformer import SNARFDeformer
         from ..networks.ngp import NeRFNGPNet
         if isinstance(deformer, SNARFDeformer) and isinstance(net, NeRFNGPNet):
-            L = _lib.lib()
             k = len(deformer.deformer.init_bones)
             # all probe sets in one launch when the sizes allow (288 GB of HBM: ~1 GB of scratch); `batched_probes = False`
             # hands over the small workspace of `ia_density_init_workspace_bytes` only: one probe set per launch, same result
-            need = L.ia_density_init_workspace_bytes(G, k)
+            need = _lib.call("ia_density_init_workspace_bytes", G, k)
             if self.batched_probes:
-                need = max(need, L.ia_density_init_workspace_bytes_batched(G, k, iters))
+                need = max(need, _lib.call("ia_density_init_workspace_bytes_batched", G, k, iters))
                 ws = self._workspace(need)
             else:
                 ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
             density = torch.empty((G, G, G), device=dev)
             out8 = torch.empty((G, G, G), dtype=torch.bool, device=dev)   # the kernel writes the bytes 0 / 1: a bool tensor's storage
             tfs = deformer.tfs.detach().float().contiguous()
-            _lib.check(L.ia_density_grid_init(_lib.ptr(jitter), iters, G, _lib.ptr(self.aabb_tensor()),
-                                              _lib.ptr(deformer.deformer.voxel_J_cl), _lib.ptr(tfs),
-                                              deformer.deformer._bones_c, k, C.byref(deformer.deformer.grid_desc()),
-                                              C.byref(net.field_desc(G * G * G * k * iters)), _lib.ptr(density), _lib.ptr(self.occ_bits),
-                                              _lib.ptr(out8), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                       "ia_density_grid_init")
+            _lib.call("ia_density_grid_init", jitter, iters, G, self.aabb_tensor(), deformer.deformer.voxel_J_cl, tfs,
+                      deformer.deformer._bones_c, k, deformer.deformer.grid_desc(), net.field_desc(G * G * G * k * iters), density,
+                      self.occ_bits, out8, ws, ws.numel())
             self.density_field = out8
             self.density_probe = density
             return
@@ -160,12 +151,10 @@ class DensityGrid(torch.nn.Module):
         if f.numel() == 0:
             raise ValueError("smpl_init needs the body model's triangle faces (body_model.faces_tensor is empty)")
         _lib.require_cuda(v)
-        L = _lib.lib()
         pts = torch.empty((G * G * G, 3), device=dev)
         sd = torch.empty(G * G * G, device=dev)
-        _lib.check(L.ia_grid_cell_centres(G, _lib.ptr(self.aabb_tensor()), _lib.ptr(pts), _lib.stream()), "ia_grid_cell_centres")
-        _lib.check(L.ia_mesh_signed_distance(_lib.ptr(pts), G * G * G, _lib.ptr(v), _lib.ptr(f), f.shape[0], _lib.ptr(sd), _lib.stream()),
-                   "ia_mesh_signed_distance")
+        _lib.call("ia_grid_cell_centres", G, self.aabb_tensor(), pts)
+        _lib.call("ia_mesh_signed_distance", pts, G * G * G, v, f, f.shape[0], sd)
         return sd.reshape(G, G, G)
 
     # -- training-time grid ---------------------------------------------------------

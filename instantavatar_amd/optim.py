@@ -9,8 +9,6 @@ maximize -- so an `optimizer_states` entry of a Lightning checkpoint written by 
 A learning-rate scheduler works as with torch's optimiser; `capturable_lr()` turns the group rates into device scalars so
 that a step captured in a HIP graph sees later changes.  There is no CPU path: the step is the HIP kernel or an error.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -87,16 +85,14 @@ class FusedAdam(torch.optim.Optimizer):
         if not items:
             return None
         dev = torch.device("cuda", torch.cuda.current_device())
-        L = _lib.lib()
         if self._ws is None or self._ws.device != dev:
-            self._ws = torch.zeros(int(L.ia_adam_workspace_bytes()), dtype=torch.uint8, device=dev)
+            self._ws = torch.zeros(int(_lib.call("ia_adam_workspace_bytes")), dtype=torch.uint8, device=dev)
             self._found = torch.zeros((), dtype=torch.float32, device=dev)
         if len(items) > _lib.IA_ADAM_MAX_TENSORS:
             raise NotImplementedError("FusedAdam: more than %d parameter tensors with gradients (the reference has at most 6)" % _lib.IA_ADAM_MAX_TENSORS)
         arr = (_lib.AdamTensor * len(items))(*items)
         skip = skip_flag.float().reshape(()).contiguous() if skip_flag is not None else None   # (named: alive until the launch is enqueued)
-        _lib.check(L.ia_adam_step(arr, len(items), _lib.ptr(skip), _lib.ptr(self._found),
-                                  1 if self.fused_zero_grad else 0, _lib.ptr(self._ws), self._ws.numel(), _lib.stream()), "ia_adam_step")
+        _lib.call("ia_adam_step", arr, len(items), skip, self._found, 1 if self.fused_zero_grad else 0, self._ws, self._ws.numel())
         self.grads_zeroed = bool(self.fused_zero_grad)
         return None
 

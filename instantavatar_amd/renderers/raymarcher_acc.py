@@ -13,8 +13,6 @@ Two test-time routes with identical results:
   * dense (instantavatar_amd/dense_routes.py): any other `model(pts, _)` callable -- the unfused
     kernels `ia_raymarch_test` / `ia_composite_test` driven from the host with the callable in between.
 """
-import ctypes as C
-
 import torch
 
 from .. import _lib
@@ -67,8 +65,7 @@ class _RaySamplesFn(torch.autograd.Function):
         dev = d_pts.device
         d_o, d_d = torch.empty((n, 3), device=dev), torch.empty((n, 3), device=dev)
         g = d_pts.float().contiguous()
-        _lib.check(_lib.lib().ia_ray_samples_bwd(_lib.ptr(st["ray_off"]), _lib.ptr(st["ray_cnt"]), _lib.ptr(st["s_z"]), _lib.ptr(g), n,
-                                                 _lib.ptr(d_o), _lib.ptr(d_d), _lib.stream()), "ia_ray_samples_bwd")
+        _lib.call("ia_ray_samples_bwd", st["ray_off"], st["ray_cnt"], st["s_z"], g, n, d_o, d_d)
         return d_o.reshape(ctx.shapes[0]), d_d.reshape(ctx.shapes[1]), None
 
 
@@ -78,7 +75,6 @@ class _SmplDeformCompactFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pts, T_inv, deformer, n_pts_dev, out):
-        L = _lib.lib()
         x = pts.detach().reshape(-1, 3).float().contiguous()
         P = x.shape[0]
         V = deformer.vertices.shape[1]
@@ -88,9 +84,8 @@ class _SmplDeformCompactFn(torch.autograd.Function):
         cand_pt, idx = torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev)
         pt_off, pt_cnt = torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.uint8, device=dev)
         n_cand = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(L.ia_smpl_nn_compact(_lib.ptr(x), P, _lib.ptr(n_pts_dev), _lib.ptr(deformer.vertices.detach()), _lib.ptr(Ti), V,
-                                        float(deformer.threshold), _lib.ptr(cand_xc), _lib.ptr(cand_pt), _lib.ptr(idx), _lib.ptr(pt_off),
-                                        _lib.ptr(pt_cnt), _lib.ptr(n_cand), deformer.nn_grid_ptr(), _lib.stream()), "ia_smpl_nn_compact")
+        _lib.call("ia_smpl_nn_compact", x, P, n_pts_dev, deformer.vertices.detach(), Ti, V, float(deformer.threshold), cand_xc, cand_pt,
+                  idx, pt_off, pt_cnt, n_cand, deformer.nn_grid_ptr())
         out.update(pt_off=pt_off, pt_cnt=pt_cnt, n_cand=n_cand)
         ctx.save_for_backward(x, Ti, cand_pt, idx, n_cand)
         ctx.shapes = (pts.shape, T_inv.shape)
@@ -106,8 +101,7 @@ class _SmplDeformCompactFn(torch.autograd.Function):
         d_pts = torch.empty((P, 3), device=dev) if need_p else None
         d_T = torch.empty((V, 4, 4), device=dev) if need_T else None
         g = d_cand.float().contiguous()
-        _lib.check(_lib.lib().ia_smpl_nn_compact_bwd(_lib.ptr(x), P, _lib.ptr(cand_pt), _lib.ptr(idx), _lib.ptr(n_cand), P, _lib.ptr(Ti), V,
-                                                     _lib.ptr(g), _lib.ptr(d_T), _lib.ptr(d_pts), _lib.stream()), "ia_smpl_nn_compact_bwd")
+        _lib.call("ia_smpl_nn_compact_bwd", x, P, cand_pt, idx, n_cand, P, Ti, V, g, d_T, d_pts)
         return (d_pts.reshape(ctx.shapes[0]) if need_p else None), (d_T.reshape(ctx.shapes[1]) if need_T else None), None, None, None
 
 
@@ -117,7 +111,6 @@ class _CompositeTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cand_rgb, cand_sigma, st):
-        L = _lib.lib()
         dev = cand_rgb.device
         n, S = st["n"], st["S"]
         cand_rgb, cand_sigma = cand_rgb.contiguous(), cand_sigma.contiguous()
@@ -129,13 +122,9 @@ class _CompositeTrainFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)   # an unused output (depth) arrives as None, not as a freshly filled zero tensor
         sv = dict(arg=torch.empty(cap, dtype=torch.int32, device=dev), sigma=torch.empty(cap, device=dev),
                   alpha=torch.empty(cap, device=dev), T=torch.empty(cap, device=dev))
-        _lib.check(L.ia_composite_train_fwd(_lib.ptr(cand_rgb), _lib.ptr(cand_sigma), cand_sigma.shape[0],
-                                            _lib.ptr(st["pt_off"]), _lib.ptr(st["pt_cnt"]),
-                                            st["n_init"], _lib.ptr(st["ray_off"]), _lib.ptr(st["ray_cnt"]), _lib.ptr(st["s_z"]),
-                                            _lib.ptr(st["near"]), _lib.ptr(st["far"]), n, S, _lib.ptr(st["noise"]), st["noise_scale"],
-                                            _lib.ptr(st["bg"]), _lib.ptr(color), _lib.ptr(depth), _lib.ptr(alpha), _lib.ptr(weights),
-                                            _lib.ptr(st["s_slot"]), _lib.ptr(sv["arg"]), _lib.ptr(sv["sigma"]), _lib.ptr(sv["alpha"]),
-                                            _lib.ptr(sv["T"]), _lib.stream()), "ia_composite_train_fwd")
+        _lib.call("ia_composite_train_fwd", cand_rgb, cand_sigma, cand_sigma.shape[0], st["pt_off"], st["pt_cnt"], st["n_init"],
+                  st["ray_off"], st["ray_cnt"], st["s_z"], st["near"], st["far"], n, S, st["noise"], st["noise_scale"], st["bg"], color,
+                  depth, alpha, weights, st["s_slot"], sv["arg"], sv["sigma"], sv["alpha"], sv["T"])
         ctx.st, ctx.sv = st, sv
         ctx.save_for_backward(cand_rgb)
         ctx.n_cand = cand_sigma.shape[0]
@@ -143,7 +132,6 @@ class _CompositeTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_color, d_depth, d_alpha, d_weights):
-        L = _lib.lib()
         st, sv = ctx.st, ctx.sv
         (cand_rgb,) = ctx.saved_tensors
         dev = cand_rgb.device
@@ -153,12 +141,9 @@ class _CompositeTrainFn(torch.autograd.Function):
         if bufs is None:       # (a second backward through the same graph: fresh buffers)
             bufs = (torch.zeros((ctx.n_cand, 3), device=dev), torch.zeros(ctx.n_cand, device=dev))
         d_rgb, d_sig = bufs
-        _lib.check(L.ia_composite_train_bwd(_lib.ptr(d_color), _lib.ptr(d_depth), _lib.ptr(d_alpha), _lib.ptr(d_weights),
-                                            _lib.ptr(cand_rgb), _lib.ptr(st["ray_off"]), _lib.ptr(st["ray_cnt"]), _lib.ptr(st["s_z"]),
-                                            _lib.ptr(st["near"]), _lib.ptr(st["far"]), st["n"], st["S"], _lib.ptr(st["bg"]),
-                                            _lib.ptr(st["s_slot"]), _lib.ptr(sv["arg"]), _lib.ptr(sv["sigma"]), _lib.ptr(sv["alpha"]),
-                                            _lib.ptr(sv["T"]), _lib.ptr(d_rgb), _lib.ptr(d_sig), _lib.stream()),
-                   "ia_composite_train_bwd")
+        _lib.call("ia_composite_train_bwd", d_color, d_depth, d_alpha, d_weights, cand_rgb, st["ray_off"], st["ray_cnt"], st["s_z"],
+                  st["near"], st["far"], st["n"], st["S"], st["bg"], st["s_slot"], sv["arg"], sv["sigma"], sv["alpha"], sv["T"], d_rgb,
+                  d_sig)
         return d_rgb, d_sig, None
 
 
@@ -234,7 +219,6 @@ class Raymarcher(torch.nn.Module):
         empty launches) and the device-side alive count is checked once at the
         end -- if rays are still alive the call is resumed.  Results are
         independent of the hint."""
-        L = _lib.lib()
         dev = rays.o.device
         o = rays.o.reshape(-1, 3).float().contiguous()
         d = rays.d.reshape(-1, 3).float().contiguous()
@@ -243,7 +227,7 @@ class Raymarcher(torch.nn.Module):
         R = o.shape[0]
         grid = self.density_grid_test
         k = len(deformer.deformer.init_bones)
-        need = L.ia_render_workspace_bytes(R, self.MAX_BATCH_SIZE, k)
+        need = _lib.call("ia_render_workspace_bytes", R, self.MAX_BATCH_SIZE, k)
         if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
             self._ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
             self._n_alive_dev = torch.zeros(2, dtype=torch.int32, device=dev)  # [alive after the last iteration, iterations executed]
@@ -254,15 +238,10 @@ class Raymarcher(torch.nn.Module):
         aabb = grid.aabb_tensor()
 
         def launch(n_iters, resume):
-            _lib.check(L.ia_render_test(_lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), R, _lib.ptr(bg),
-                                        _lib.ptr(grid.occ_bits), grid.grid_size, _lib.ptr(aabb),
-                                        _lib.ptr(deformer.deformer.voxel_J_cl), _lib.ptr(tfs), deformer.deformer._bones_c,
-                                        k, C.byref(deformer.deformer.grid_desc()),
-                                        C.byref(net.field_desc(self.MAX_BATCH_SIZE * k)),
-                                        self.MAX_SAMPLES, self.MAX_BATCH_SIZE, n_iters, resume, _lib.ptr(rgb),
-                                        _lib.ptr(depth), _lib.ptr(alpha), _lib.ptr(counter),
-                                        _lib.ptr(self._n_alive_dev), _lib.ptr(self._ws), self._ws.numel(),
-                                        _lib.stream()), "ia_render_test")
+            _lib.call("ia_render_test", o, d, near, far, R, bg, grid.occ_bits, grid.grid_size, aabb, deformer.deformer.voxel_J_cl, tfs,
+                      deformer.deformer._bones_c, k, deformer.deformer.grid_desc(), net.field_desc(self.MAX_BATCH_SIZE * k),
+                      self.MAX_SAMPLES, self.MAX_BATCH_SIZE, n_iters, resume, rgb, depth, alpha, counter, self._n_alive_dev, self._ws,
+                      self._ws.numel())
 
         total = self._iters_hint
         launch(total, 0)
@@ -298,7 +277,6 @@ class Raymarcher(torch.nn.Module):
         step (`training.StepState`) the random draws come from the step, and the pool and the overflow source go to it."""
         from ..deformers.smpl_deformer import SMPLDeformer
         smpl = isinstance(deformer, SMPLDeformer)
-        L = _lib.lib()
         dev = rays.o.device
         o = rays.o.reshape(-1, 3).float().contiguous()
         d = rays.d.reshape(-1, 3).float().contiguous()
@@ -326,11 +304,8 @@ class Raymarcher(torch.nn.Module):
         jitter = draw("ray_jitter", torch.rand)                                   # :156
         grid = self.density_grid_train
         with torch.no_grad():
-            _lib.check(L.ia_march_train_compact(_lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), n, _lib.ptr(grid.occ_bits),
-                                                C.byref(self._occ_desc_cached(grid)), S, _lib.ptr(jitter), _lib.ptr(st["s_pts"]),
-                                                _lib.ptr(st["s_z"]), _lib.ptr(st["s_slot"]), _lib.ptr(st["ray_off"]),
-                                                _lib.ptr(st["ray_cnt"]), _lib.ptr(st["n_samples"]), cap, _lib.stream()),
-                       "ia_march_train_compact")
+            _lib.call("ia_march_train_compact", o, d, near, far, n, grid.occ_bits, self._occ_desc_cached(grid), S, jitter, st["s_pts"],
+                      st["s_z"], st["s_slot"], st["ray_off"], st["ray_cnt"], st["n_samples"], cap)
         if smpl:
             pts = _RaySamplesFn.apply(o, d, st)
             cand = _SmplDeformCompactFn.apply(pts, deformer.T_inv, deformer, st["n_samples"], st)

@@ -15,8 +15,6 @@
   occupancy densities every 20 steps.
 * `GraphedTrainStep`: the whole step captured into a HIP graph and replayed.
 """
-import ctypes as C
-
 import torch
 import torch.nn.functional as F
 
@@ -142,10 +140,9 @@ class _FieldFn(torch.autograd.Function):
     def forward(ctx, x, enc_params, col_params, net, n_dev, pool):
         """n_dev: optional device int32[1] live count -- x is then a capacity-sized buffer whose
         tail is never read; outputs past the count are zero (slices of `pool` when it can serve them)."""
-        L = _lib.lib()
         xc = x.detach().reshape(-1, 3).float().contiguous()
         V = xc.shape[0]
-        stride = L.ia_field_act_stride(net.n_levels)
+        stride = _lib.call("ia_field_act_stride", net.n_levels)
         acts = torch.empty((V, stride), device=x.device, dtype=torch.float16)
         alloc = (lambda shp: pooled_zeros(pool, shp, x.device)) if n_dev is not None else (lambda shp: torch.empty(shp, device=x.device))
         rgb = alloc((V, 3))
@@ -154,8 +151,7 @@ class _FieldFn(torch.autograd.Function):
         split = desc.enc_split
         desc.enc_split = int(getattr(net, "enc_split_train", split))   # (the training batches' own XCD balance hint: see NeRFNGPNet)
         try:
-            _lib.check(L.ia_field_fwd_train(_lib.ptr(xc), V, _lib.ptr(n_dev), C.byref(desc), _lib.ptr(rgb),
-                                            _lib.ptr(sigma), _lib.ptr(acts), _lib.stream()), "ia_field_fwd_train")
+            _lib.call("ia_field_fwd_train", xc, V, n_dev, desc, rgb, sigma, acts)
         finally:
             desc.enc_split = split
         ctx.net = net
@@ -181,13 +177,11 @@ class _FieldFn(torch.autograd.Function):
         d_sigma = d_sigma.reshape(V).float().contiguous()
         # gradients are rescaled per call so that their largest magnitude sits at 2^10 before the
         # cast to half (tcnn relies on a fixed 1024x loss scale, DNeRF.py:58); device scalar, no sync, one launch
-        L = _lib.lib()
         S = torch.empty(1, device=xc.device)
         state = getattr(net, "_grad_scale_state", None)
         if state is None or state.device != xc.device:
             state = net._grad_scale_state = torch.zeros(2, dtype=torch.int32, device=xc.device)
-        _lib.check(L.ia_field_grad_scale(_lib.ptr(rgb), _lib.ptr(d_rgb), _lib.ptr(d_sigma), V, _lib.ptr(ctx.n_dev), _lib.ptr(state),
-                                         _lib.ptr(S), _lib.stream()), "ia_field_grad_scale")
+        _lib.call("ia_field_grad_scale", rgb, d_rgb, d_sigma, V, ctx.n_dev, state, S)
         # a frozen parameter vector (requires_grad False: eval.py:70-73 freezes the field and optimises the SMPL tables only)
         # keeps `.grad` None, as autograd would leave it -- the kernels still need somewhere to accumulate: a scratch buffer
         enc_live, col_live = net.encoder.params.requires_grad, net.color_net.params.requires_grad
@@ -197,11 +191,9 @@ class _FieldFn(torch.autograd.Function):
         if FUSED_MLP_BACKWARD:
             dfeat = torch.empty((V, nf), device=xc.device)
             base_e, base_c = g_enc.data_ptr(), g_col.data_ptr()
-            ws = torch.empty(int(L.ia_field_bwd_workspace_bytes(V, net.n_levels)), dtype=torch.uint8, device=xc.device)
-            _lib.check(L.ia_field_bwd(_lib.ptr(acts), _lib.ptr(rgb), _lib.ptr(d_rgb), _lib.ptr(d_sigma), V,
-                                      _lib.ptr(ctx.n_dev), _lib.ptr(S), C.byref(net.field_desc()), _lib.ptr(dfeat), base_e,
-                                      base_e + 4 * n1, base_c, base_c + 4 * 1024, base_c + 4 * 5120, _lib.ptr(ws), ws.numel(),
-                                      _lib.stream()), "ia_field_bwd")
+            ws = torch.empty(int(_lib.call("ia_field_bwd_workspace_bytes", V, net.n_levels)), dtype=torch.uint8, device=xc.device)
+            _lib.call("ia_field_bwd", acts, rgb, d_rgb, d_sigma, V, ctx.n_dev, S, net.field_desc(), dfeat, base_e, base_e + 4 * n1, base_c,
+                      base_c + 4 * 1024, base_c + 4 * 5120, ws, ws.numel())
         else:
             dfeat = _mlp_backward_gemm(net, acts, rgb, d_rgb, d_sigma, S, g_enc, g_col)
         w_end = n1 + 1024
@@ -215,14 +207,10 @@ class _FieldFn(torch.autograd.Function):
             # group is scattered.  The MLP weight gradients travel with the last (small, dense-level) bucket.
             red.reduce_async(g_col)
             for (l0, l1), (lo, hi) in gradient_buckets(net):
-                _lib.check(L.ia_hashgrid_bwd_levels(_lib.ptr(xc), V, _lib.ptr(ctx.n_dev), C.byref(net.field_desc()),
-                                                    _lib.ptr(dfeat), dtable.data_ptr(), l0, l1, _lib.stream()),
-                           "ia_hashgrid_bwd_levels")
+                _lib.call("ia_hashgrid_bwd_levels", xc, V, ctx.n_dev, net.field_desc(), dfeat, dtable.data_ptr(), l0, l1)
                 red.reduce_async(g_enc[lo:hi])
         else:
-            _lib.check(L.ia_hashgrid_bwd(_lib.ptr(xc), V, _lib.ptr(ctx.n_dev), C.byref(net.field_desc()),
-                                         _lib.ptr(dfeat), dtable.data_ptr(), _lib.ptr(dx), _lib.stream()),
-                       "ia_hashgrid_bwd")
+            _lib.call("ia_hashgrid_bwd", xc, V, ctx.n_dev, net.field_desc(), dfeat, dtable.data_ptr(), dx)
         return dx, None, None, None, None, None
 
 
@@ -332,9 +320,7 @@ def _nerf_loss_kernel(rgb, alpha, weight, tgt_rgb, tgt_alpha, w_rgb, w_alpha, w_
     cnt, cap = overflow_src if overflow_src is not None else (None, 0)
     if cnt is not None:
         assert cnt.dtype == torch.int32 and cnt.is_cuda and cnt.numel() >= 1, "overflow counter: device int32"
-    _lib.check(_lib.lib().ia_nerf_loss(_lib.ptr(r), _lib.ptr(tr), _lib.ptr(a), _lib.ptr(ta), _lib.ptr(w), a.numel(),
-                                       w.numel(), w_rgb, w_alpha, w_reg, None, _lib.ptr(cnt), int(cap), _lib.ptr(out),
-                                       _lib.ptr(d_r), _lib.ptr(d_a), _lib.ptr(d_w), _lib.stream()), "ia_nerf_loss")
+    _lib.call("ia_nerf_loss", r, tr, a, ta, w, a.numel(), w.numel(), w_rgb, w_alpha, w_reg, None, cnt, int(cap), out, d_r, d_a, d_w)
     return out, d_r, d_a, d_w
 
 
@@ -621,7 +607,7 @@ def training_step(model, batch, optimizer, loss_fn, world_size=1, is_refine=Fals
             tr = batch["transl"].detach().reshape(-1)[:3].float().contiguous()
             if tr.is_cuda and batch["near"].is_cuda:
                 near, far = torch.empty_like(batch["near"], dtype=torch.float32).contiguous(), torch.empty_like(batch["far"], dtype=torch.float32).contiguous()
-                _lib.check(_lib.lib().ia_near_far(_lib.ptr(tr), near.numel(), _lib.ptr(near), _lib.ptr(far), _lib.stream()), "ia_near_far")
+                _lib.call("ia_near_far", tr, near.numel(), near, far)
                 batch["near"], batch["far"] = near, far
             else:
                 dist = torch.norm(batch["transl"], dim=-1, keepdim=True).detach()

@@ -25,16 +25,14 @@ def nonzero_select(mask2d, window, u, without_replacement=False):
     H, W = mask2d.shape
     y0, y1, x0, x1 = window
     n = u.numel()
-    L = _lib.lib()
     dev = mask2d.device
     row = torch.empty(n, dtype=torch.int32, device=dev)
     col = torch.empty(n, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = _ws(L.ia_nonzero_select_workspace_bytes(y1 - y0, n), dev)
+    ws = _ws(_lib.call("ia_nonzero_select_workspace_bytes", y1 - y0, n), dev)
     m = mask2d.float().contiguous()
     uu = u.float().contiguous()
-    _lib.check(L.ia_nonzero_select(_lib.ptr(m), H, W, y0, y1, x0, x1, _lib.ptr(uu), n, int(without_replacement), _lib.ptr(row),
-                                   _lib.ptr(col), _lib.ptr(count), _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_nonzero_select")
+    _lib.call("ia_nonzero_select", m, H, W, y0, y1, x0, x1, uu, n, int(without_replacement), row, col, count, ws, ws.numel())
     return row, col, count
 
 
@@ -56,12 +54,10 @@ class EdgeSampler:
         ends.  The same kernel, called on an (H*W) x 1 image.  Returned in the mask's 2-D shape."""
         _lib.require_cuda(mask2d)
         H, W = mask2d.shape
-        L = _lib.lib()
         m = mask2d.float().contiguous()
         edge = torch.empty_like(m)
-        ws = _ws(L.ia_mask_edge_workspace_bytes(H * W, 1), m.device)
-        _lib.check(L.ia_mask_edge(_lib.ptr(m), H * W, 1, self.kernel_size, _lib.ptr(edge), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                   "ia_mask_edge")
+        ws = _ws(_lib.call("ia_mask_edge_workspace_bytes", H * W, 1), m.device)
+        _lib.call("ia_mask_edge", m, H * W, 1, self.kernel_size, edge, ws, ws.numel())
         return edge
 
     def sample_indices(self, mask2d, draws=None, generator=None):
@@ -81,8 +77,7 @@ class EdgeSampler:
         # (it was ~20 small torch launches of a 1.2 ms refine step).
         out = torch.empty(n, dtype=torch.int32, device=dev)
         d = draws[:n].float().contiguous()
-        _lib.check(_lib.lib().ia_edge_indices(_lib.ptr(r_m), _lib.ptr(c_m), _lib.ptr(r_e), _lib.ptr(c_e), _lib.ptr(d), self.num_mask, self.num_edge,
-                                              self.num_rand, H, W, _lib.ptr(out), _lib.stream()), "ia_edge_indices")
+        _lib.call("ia_edge_indices", r_m, c_m, r_e, c_e, d, self.num_mask, self.num_edge, self.num_rand, H, W, out)
         return out
 
     def sample(self, mask, *args, draws=None, generator=None):
@@ -112,11 +107,10 @@ class PatchSampler:
             return mask2d
         _lib.require_cuda(mask2d)
         H, W = mask2d.shape
-        L = _lib.lib()
         m = mask2d.float().contiguous()
         out = torch.empty_like(m)
-        ws = _ws(L.ia_mask_edge_workspace_bytes(H, W), m.device)
-        _lib.check(L.ia_mask_dilate(_lib.ptr(m), H, W, int(self.dilate), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream()), "ia_mask_dilate")
+        ws = _ws(_lib.call("ia_mask_edge_workspace_bytes", H, W), m.device)
+        _lib.call("ia_mask_dilate", m, H, W, int(self.dilate), out, ws, ws.numel())
         return (out > 0).float()
 
     def sample_corners(self, mask2d, draws=None, generator=None):
@@ -134,8 +128,7 @@ class PatchSampler:
         r_m, c_m, count = nonzero_select(self._candidates(mask2d), (o, H - o, o, W - o), draws[1:1 + self.n], without_replacement=True)
         rows = torch.empty(self.n, dtype=torch.int32, device=dev)
         cols = torch.empty(self.n, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().ia_patch_corners(_lib.ptr(r_m), _lib.ptr(c_m), _lib.ptr(draws), self.n, H, W, P, float(self.p),
-                                               _lib.ptr(rows), _lib.ptr(cols), _lib.stream()), "ia_patch_corners")
+        _lib.call("ia_patch_corners", r_m, c_m, draws, self.n, H, W, P, float(self.p), rows, cols)
         return rows, cols
 
     def sample(self, mask, *args, draws=None, generator=None):

@@ -30,6 +30,64 @@ def test_cabi_exports_every_declared_symbol():
     assert not missing, "symbols declared in include/*.h but not exported: %s" % missing
     assert set(_lib.EXPORTED) <= declared
     assert _lib.lib().ia_version() >= 100
+    # every declared function is bound, with as many argtypes as the header declares parameters
+    assert set(_lib.EXPORTED) == declared
+    hdr_code = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    for name in sorted(declared):
+        (arglist,) = re.findall(r"\b%s\s*\(([^()]*)\)\s*;" % name, hdr_code)
+        n_declared = 0 if arglist.strip() in ("", "void") else arglist.count(",") + 1
+        assert len(getattr(_lib.lib(), name).argtypes) == n_declared, name
+
+
+def test_binding_is_parsed_from_the_header():
+    """`_lib` derives restype / argtypes from include/instantavatar_hip.h: 89 prototypes, the 62 that launch end in
+    `void *stream` (the other 27: workspace sizes, descriptors, profile getters, the version / error / manifest strings)."""
+    from instantavatar_amd import _lib
+    decls = _lib.declarations()
+    assert len(decls) == 89
+    assert sum(d.stream for d in decls.values()) == 62
+    d = decls["ia_near_far"]
+    assert d.restype is C.c_int and [p.name for p in d.params] == ["transl", "n", "near_out", "far_out", "stream"]
+    assert [p.kind for p in d.params] == ["pointer", "scalar", "pointer", "pointer", "pointer"]
+    assert d.params[0].of == (torch.float32,) and d.params[1].ctype is C.c_int and d.params[4].of is None
+    assert decls["ia_field_fwd"].params[3].ctype is C.POINTER(_lib.Field)
+    assert decls["ia_raymarch_test"].params[4].of == (torch.int64,)
+    assert decls["ia_nerf_loss"].params[6].ctype is C.c_longlong
+    assert decls["ia_render_workspace_bytes"].restype is C.c_size_t and decls["ia_last_error"].restype is C.c_char_p
+
+
+@pytest.mark.parametrize("snippet, names", [
+    ("int ia_x(const float *a, half *b, void *stream);", ("ia_x", "half *b")),                 # a type the binding does not know
+    ("int ia_y(const float *a, void (*done)(int), void *stream);", ("ia_y", "(*done)")),      # a function pointer
+    ("int ia_z(float **rows, int n);", ("ia_z", "float **rows")),                               # a pointer to pointers
+    ("float ia_w(int n);", ("ia_w",)),                                                          # a return type it does not know
+])
+def test_header_parser_refuses_what_it_cannot_classify(snippet, names):
+    """nothing is skipped or bound loosely: the error names the function and the parameter"""
+    from instantavatar_amd import _lib
+    with pytest.raises(ImportError) as e:
+        _lib.parse_header("/* c */\n#define X 1\nint ia_ok(int n);\n" + snippet)
+    for n in names:
+        assert n in str(e.value), str(e.value)
+
+
+def test_ctypes_mirrors_list_the_header_structs_fields_in_order():
+    """The six ctypes.Structure mirrors in _lib are kept by hand: same field names, same order as the header's structs."""
+    from instantavatar_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "instantavatar_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    mirrors = {"ia_snarf_grid": _lib.SnarfGrid, "ia_hash_desc": _lib.HashDesc, "ia_field": _lib.Field, "ia_occ_grid": _lib.OccGrid,
+               "ia_adam_tensor": _lib.AdamTensor, "ia_smpl_body": _lib.SmplBody}
+    structs = dict((name, body) for body, name in re.findall(r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;", hdr, flags=re.S))
+    assert set(structs) == set(mirrors)
+    for name, body in structs.items():
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            # `int D, H, W` / `const uint16_t *sig_w1, *sig_w2` / `float offset[3]`: the last identifier of every declarator
+            first, *more = re.sub(r"\[[^\]]*\]", "", decl).split(",")
+            for declarator in [first.split()[-1]] + more:
+                fields.append(re.fullmatch(r"\s*\**\s*(\w+)\s*", declarator).group(1))
+        assert fields == [f[0] for f in mirrors[name]._fields_], name
 
 
 def test_library_manifest_equals_checkout_and_names_device_code():

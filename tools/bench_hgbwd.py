@@ -1,6 +1,5 @@
 """Dev tool: where does k_hashgrid_bwd spend its time?  Times the scatter per level group on the canonical samples of a
 real frame (ray-major order, as the training step produces them) and on the same samples shuffled."""
-import ctypes as C
 import os
 import sys
 
@@ -19,18 +18,17 @@ poses, tr = syn.procedural_pose_track(8)
 x = bench.frame_coherent_samples(model, make_batch(dev, 512, poses[1], tr[1]), 512)[:180000].contiguous()
 net = model.net_coarse
 V = x.shape[0]
-L = _lib.lib()
 dfeat = torch.randn((V, 32), device=dev) * 1e-3
 dtable = torch.zeros(2 * net.n_entries, device=dev)
 
 
 def t(l0, l1, xx, reps=20):
     for _ in range(3):
-        _lib.check(L.ia_hashgrid_bwd_levels(_lib.ptr(xx), V, None, C.byref(net.field_desc()), _lib.ptr(dfeat), dtable.data_ptr(), l0, l1, _lib.stream()))
+        _lib.call("ia_hashgrid_bwd_levels", xx, V, None, net.field_desc(), dfeat, dtable.data_ptr(), l0, l1)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(reps):
-        _lib.check(L.ia_hashgrid_bwd_levels(_lib.ptr(xx), V, None, C.byref(net.field_desc()), _lib.ptr(dfeat), dtable.data_ptr(), l0, l1, _lib.stream()))
+        _lib.call("ia_hashgrid_bwd_levels", xx, V, None, net.field_desc(), dfeat, dtable.data_ptr(), l0, l1)
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / reps * 1e3

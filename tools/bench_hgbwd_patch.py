@@ -1,6 +1,5 @@
 """Dev tool: k_hashgrid_bwd per level on the candidates of a PATCH batch (4 patches of 32 x 32 rays on the body, as the
 reference's default sampler draws them): neighbouring rays hit the same coarse cells from different waves."""
-import ctypes as C
 import os
 import sys
 
@@ -41,18 +40,17 @@ n = int(sc["n_cand"].item())
 x = sc["cand_xc"][:n].contiguous()
 net = model.net_coarse
 V = x.shape[0]
-L = _lib.lib()
 dfeat = torch.randn((V, 32), device=dev) * 1e-3
 dtable = torch.zeros(2 * net.n_entries, device=dev)
 
 
 def t_(l0, l1, xx, reps=10):
     for _ in range(2):
-        _lib.check(L.ia_hashgrid_bwd_levels(_lib.ptr(xx), V, None, C.byref(net.field_desc()), _lib.ptr(dfeat), dtable.data_ptr(), l0, l1, _lib.stream()))
+        _lib.call("ia_hashgrid_bwd_levels", xx, V, None, net.field_desc(), dfeat, dtable.data_ptr(), l0, l1)
     a, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(reps):
-        _lib.check(L.ia_hashgrid_bwd_levels(_lib.ptr(xx), V, None, C.byref(net.field_desc()), _lib.ptr(dfeat), dtable.data_ptr(), l0, l1, _lib.stream()))
+        _lib.call("ia_hashgrid_bwd_levels", xx, V, None, net.field_desc(), dfeat, dtable.data_ptr(), l0, l1)
     b_.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b_) / reps * 1e3

@@ -1,5 +1,4 @@
 """Dev tool: ia_precompute in isolation (events on the launch stream), with and without voxel_d / bbox."""
-import ctypes as C
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -15,18 +14,16 @@ model.deformer.prepare_deformer(b)
 fd = model.deformer.deformer
 tfs = model.deformer.tfs.detach().float().contiguous()
 fr = fd._frame
-L = _lib.lib()
 
 
 def run(want_d, want_bbox, n=200):
-    args = (_lib.ptr(fd.lbs_voxel_final), _lib.ptr(tfs), _lib.ptr(fr["J"]), _lib.ptr(fr["d"]) if want_d else None,
-            _lib.ptr(fr["bbox"]) if want_bbox else None, C.byref(fd.grid_desc()), _lib.stream())
+    args = (fd.lbs_voxel_final, tfs, fr["J"], fr["d"] if want_d else None, fr["bbox"] if want_bbox else None, fd.grid_desc())
     for _ in range(10):
-        _lib.check(L.ia_precompute(*args))
+        _lib.call("ia_precompute", *args)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(n):
-        _lib.check(L.ia_precompute(*args))
+        _lib.call("ia_precompute", *args)
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
@@ -34,15 +31,14 @@ def run(want_d, want_bbox, n=200):
 
 def run_ws(n=200):
     """the product's call: voxel_d + bounding box through per-workgroup extrema (ia_precompute_ws)"""
-    ws = torch.empty(int(L.ia_precompute_workspace_bytes(C.byref(fd.grid_desc()))), dtype=torch.uint8, device=dev)
-    args = (_lib.ptr(fd.lbs_voxel_final), _lib.ptr(tfs), _lib.ptr(fr["J"]), _lib.ptr(fr["d"]), _lib.ptr(fr["bbox"]), C.byref(fd.grid_desc()),
-            _lib.ptr(ws), ws.numel(), _lib.stream())
+    ws = torch.empty(int(_lib.call("ia_precompute_workspace_bytes", fd.grid_desc())), dtype=torch.uint8, device=dev)
+    args = (fd.lbs_voxel_final, tfs, fr["J"], fr["d"], fr["bbox"], fd.grid_desc(), ws, ws.numel())
     for _ in range(10):
-        _lib.check(L.ia_precompute_ws(*args))
+        _lib.call("ia_precompute_ws", *args)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(n):
-        _lib.check(L.ia_precompute_ws(*args))
+        _lib.call("ia_precompute_ws", *args)
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1) / n * 1e3

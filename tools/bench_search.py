@@ -1,6 +1,5 @@
 """Dev tool: ia_snarf_search_compact in isolation on the sample points of a real 512^2 frame (64 march steps around the
 surface of every hit ray, ray-major) and on the 64^3 x 5 probe points; events on the launch stream."""
-import ctypes as C
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -33,7 +32,6 @@ dd = model.deformer
 fd = dd.deformer
 k = len(fd.init_bones)
 P = pts.shape[0]
-L = _lib.lib()
 cand = torch.empty((P * k, 3), device=dev)
 pt_off = torch.empty(P, dtype=torch.int32, device=dev)
 pt_cnt = torch.empty(P, dtype=torch.uint8, device=dev)
@@ -44,9 +42,8 @@ tfs = dd.tfs.detach().float().contiguous()
 def run(n=30):
     def once():
         n_cand.zero_()
-        _lib.check(L.ia_snarf_search_compact(_lib.ptr(pts), P, None, _lib.ptr(fd.voxel_J_cl), _lib.ptr(tfs), fd._bones_c, k,
-                                             C.byref(fd.grid_desc()), 1e-5, 1e-1, _lib.ptr(cand), P * k, _lib.ptr(pt_off), _lib.ptr(pt_cnt),
-                                             _lib.ptr(n_cand), 0, _lib.stream()))
+        _lib.call("ia_snarf_search_compact", pts, P, None, fd.voxel_J_cl, tfs, fd._bones_c, k, fd.grid_desc(), 1e-5, 1e-1, cand, P * k,
+                  pt_off, pt_cnt, n_cand, 0)
     for _ in range(5):
         once()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
