@@ -292,14 +292,12 @@ __device__ __forceinline__ void encode_all(const FieldDev &F, const uint32_t *__
 // level-major planes [L][stride] of packed half2 (coalesced 256 B per wave) and
 // consumed by k_field<..., PLANES>.  Per-level arithmetic is identical to
 // level_loads/level_reduce, so the features are bit-identical.
-// Hashed levels use the x-neighbour pairing: for even cx the two corners differ in
-// index bit 0 only -> one aligned 8-byte load; odd cx adds a predicated 4-byte load.
+// Hashed levels gather the aligned 16-byte group of four entries around corner x: the
+// x-neighbour (x + 1) ^ h lies in the same group unless x mod 4 == 3 -> one 16-byte load
+// per (y, z) pair; one lane in four adds a predicated 4-byte load (hashed_quad_loads).
 // ---------------------------------------------------------------------------
-#ifndef IA_ENC_QUAD
-#define IA_ENC_QUAD 1  // hashed levels: one aligned 16-byte group of four entries per (y, z) pair (see hashed_quad_loads)
-#endif
 #ifndef IA_ENC_S
-#define IA_ENC_S (IA_ENC_QUAD ? 3 : 4)  // samples per thread (table gathers in flight per lane: 4-5 (group) or 4-8 (pair) per sample)
+#define IA_ENC_S 3  // samples per thread (table gathers in flight per lane: 4-5 per sample)
 #endif
 #define IA_ENC_THREADS 256
 #define IA_ENC_TILE (IA_ENC_S * IA_ENC_THREADS)
@@ -307,91 +305,15 @@ __device__ __forceinline__ void encode_all(const FieldDev &F, const uint32_t *__
 #define IA_ENC_MAX_WG_PER_XCD 256  // 32 CUs x 8 resident workgroups
 #endif
 
-// Cache policy of a table gather (MI355X_MICROARCH.md: `nt` / `sc1` loads bypass the CU's vector L1 and are served by the
-// XCD's L2 -- no 128-byte line fill into the TCP for an entry nobody on this CU will touch again): 0 = default
-// (L1-allocating), 1 = nt, 2 = sc1 (relaxed agent-scope load).  Values are identical whatever the policy.
-template <int POL>
-__device__ __forceinline__ uint32_t gather32(const uint32_t *p) {
-  if (POL == 1) return __builtin_nontemporal_load(p);
-  if (POL == 2) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return *p;
-}
-template <int POL>
-__device__ __forceinline__ uint2 gather64(const uint32_t *p) {  // p 8-byte aligned
-  union { unsigned long long q; uint2 u; } c;
-  const unsigned long long *q = reinterpret_cast<const unsigned long long *>(p);
-  if (POL == 1) c.q = __builtin_nontemporal_load(q);
-  else if (POL == 2) c.q = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else c.q = *q;
-  return c.u;
-}
-#ifndef IA_ENC_POL_H_LO
-#define IA_ENC_POL_H_LO 0  // hashed levels 4..7  (XCD-sharded encoder)
-#endif
-#ifndef IA_ENC_POL_H_HI
-#define IA_ENC_POL_H_HI 0  // hashed levels 8..15 (XCD-sharded encoder)
-#endif
-
-template <int POL>
-__device__ __forceinline__ void hashed_pair_loads(const uint32_t *__restrict__ tab, float scale, uint32_t mask,
-                                                  const float xn[3], float w[3], uint32_t px[4], uint32_t py[4],
-                                                  uint32_t ext[4], uint32_t &meta) {
-  uint32_t g[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    const float pos = __builtin_fmaf(xn[d], scale, 0.5f);
-    const float fl = floorf(pos);
-    g[d] = (uint32_t)(int)fl;
-    w[d] = pos - fl;
-  }
-  const bool odd = g[0] & 1u;
-  meta = odd ? 16u : 0u;
-#pragma unroll
-  for (int pr = 0; pr < 4; pr++) {
-    const uint32_t cy = g[1] + (pr & 1), cz = g[2] + (pr >> 1);
-    const uint32_t hsh = (cy * 2654435761u) ^ (cz * 805459861u);
-    const uint32_t i0 = (g[0] ^ hsh) & mask;
-    const uint2 pair = gather64<POL>(tab + (i0 & ~1u));
-    px[pr] = pair.x;
-    py[pr] = pair.y;
-    meta |= (i0 & 1u) << pr;
-    ext[pr] = 0u;
-    if (odd) ext[pr] = gather32<POL>(tab + (((g[0] + 1) ^ hsh) & mask));
-  }
-}
-
-__device__ __forceinline__ uint32_t hashed_pair_reduce(const float w[3], const uint32_t px[4], const uint32_t py[4],
-                                                       const uint32_t ext[4], uint32_t meta) {
-  _Float16 r0 = (_Float16)0.f, r1 = (_Float16)0.f;
-  const bool odd = meta & 16u;
-#pragma unroll
-  for (int idx = 0; idx < 8; idx++) {
-    float wt = 1.f;
-    wt *= (idx & 1) ? w[0] : 1.f - w[0];
-    wt *= (idx & 2) ? w[1] : 1.f - w[1];
-    wt *= (idx & 4) ? w[2] : 1.f - w[2];
-    const int pr = idx >> 1;
-    const bool hi0 = (meta >> pr) & 1u;  // corner cx sits in the upper half of its aligned pair
-    const uint32_t c0 = hi0 ? py[pr] : px[pr];
-    const uint32_t c1 = odd ? ext[pr] : (hi0 ? px[pr] : py[pr]);
-    union { uint32_t u; half2v h; } c;
-    c.u = (idx & 1) ? c1 : c0;
-    r0 = r0 + (_Float16)(wt * (float)c.h.x);
-    r1 = r1 + (_Float16)(wt * (float)c.h.y);
-  }
-  union { uint32_t u; half2v h; } o;
-  o.h.x = r0; o.h.y = r1;
-  return o.u;
-}
-
-// IA_ENC_QUAD (round 6): the aligned 16-byte GROUP of four table entries around corner x instead of its aligned pair.  With tcnn's
+// Round 6: the aligned 16-byte GROUP of four table entries around corner x instead of its aligned pair.  With tcnn's
 // hash the x-neighbour of a corner is entry (x + 1) ^ h: inside the same aligned pair when x is even, inside the same aligned group
 // of four unless x mod 4 == 3.  One dwordx4 gather per (y, z) pair then serves both x-corners for 3 lanes in 4 (the pair version: 2
 // in 4), and the second, separate gather of the others touches a quarter instead of half of the wave's lanes: 4 x 64 + 4 x 16 = 320
 // line look-ups per wave and level instead of 4 x 64 + 4 x 32 = 384 -- the vector L1's look-up rate is what bounds this kernel.
-// Measured (tools/ab_encode_quad.sh, profiles/r06_ab_encode_quad.txt): 2^20 random points 342 -> 325 us, a frame's samples 204 -> 190 us,
+// Measured (profiles/r06_ab_encode_quad.txt): 2^20 random points 342 -> 325 us, a frame's samples 204 -> 190 us,
 // features bit-identical; 578 -> 587-589 frames/s.  Three samples per thread (122 VGPRs, four waves per SIMD) instead of four with the
-// wider records (160 VGPRs otherwise); the pair version (IA_ENC_QUAD=0, IA_ENC_S=4) stays for A/B runs.
+// wider records (160 VGPRs otherwise).  The pair version and its cache policies: tools/variants/encode_pair_r06.diff.txt,
+// tools/variants/encode_cache_policy_r06.diff.txt.
 __device__ __forceinline__ uint32_t quad_select(uint32_t x, uint32_t y, uint32_t z, uint32_t w, uint32_t s) {
   const uint32_t lo = (s & 1u) ? y : x, hi = (s & 1u) ? w : z;
   return (s & 2u) ? hi : lo;
@@ -426,7 +348,7 @@ __device__ __forceinline__ uint32_t hashed_quad_reduce(const float w[3], const u
   _Float16 r0 = (_Float16)0.f, r1 = (_Float16)0.f;
   const bool far = meta & (1u << 16);
 #pragma unroll
-  for (int idx = 0; idx < 8; idx++) {   // the same eight weighted fp16 accumulations, in the same order, as hashed_pair_reduce
+  for (int idx = 0; idx < 8; idx++) {   // the same eight weighted fp16 accumulations, in the same order, as level_reduce
     float wt = 1.f;
     wt *= (idx & 1) ? w[0] : 1.f - w[0];
     wt *= (idx & 2) ? w[1] : 1.f - w[1];
@@ -485,7 +407,6 @@ __global__ __launch_bounds__(IA_ENC_THREADS) void k_encode_xcd(const float *__re
       const float scale = F.lv.scale[lev_h];
       float w[IA_ENC_S][3];
       uint32_t *out = planes + (size_t)lev_h * stride;
-#if IA_ENC_QUAD
       uint32_t qx[IA_ENC_S][4], qy[IA_ENC_S][4], qz[IA_ENC_S][4], qw[IA_ENC_S][4], ext[IA_ENC_S][4], meta[IA_ENC_S];
 #pragma unroll
       for (int k = 0; k < IA_ENC_S; k++) hashed_quad_loads(tab, scale, F.hash_size - 1, xn[k], w[k], qx[k], qy[k], qz[k], qw[k], ext[k], meta[k]);
@@ -495,22 +416,6 @@ __global__ __launch_bounds__(IA_ENC_THREADS) void k_encode_xcd(const float *__re
         const uint32_t f = hashed_quad_reduce(w[k], qx[k], qy[k], qz[k], qw[k], ext[k], meta[k]);
         if (i < V) out[i] = f;
       }
-#else
-      uint32_t px[IA_ENC_S][4], py[IA_ENC_S][4], ext[IA_ENC_S][4], meta[IA_ENC_S];
-      if (IA_ENC_POL_H_LO != IA_ENC_POL_H_HI && lev_h - ND < 4) {  // (wave-uniform)
-#pragma unroll
-        for (int k = 0; k < IA_ENC_S; k++) hashed_pair_loads<IA_ENC_POL_H_LO>(tab, scale, F.hash_size - 1, xn[k], w[k], px[k], py[k], ext[k], meta[k]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < IA_ENC_S; k++) hashed_pair_loads<IA_ENC_POL_H_HI>(tab, scale, F.hash_size - 1, xn[k], w[k], px[k], py[k], ext[k], meta[k]);
-      }
-#pragma unroll
-      for (int k = 0; k < IA_ENC_S; k++) {
-        const int i = base + k * IA_ENC_THREADS;
-        const uint32_t f = hashed_pair_reduce(w[k], px[k], py[k], ext[k], meta[k]);
-        if (i < V) out[i] = f;
-      }
-#endif
     }
     if (lev_d >= 0) {
       const uint32_t *tab = F.table + F.lv.offset[lev_d];
@@ -1246,9 +1151,6 @@ extern "C" int ia_field_bwd(const uint16_t *acts, const float *rgb, const float 
 #define IA_HGB_REDUCE_LEVELS 8
 #endif
 
-#ifndef IA_HGB_QUAD
-#define IA_HGB_QUAD 1
-#endif
 // one round of the quad-cooperative scatter: every lane of a quad reads the operands of quad lane R (DPP quad_perm) and
 // adds its own word of that sample's (x0, x1) entry pair
 template <int R>
@@ -1327,10 +1229,8 @@ __global__ __launch_bounds__(256) void k_hashgrid_bwd(const float *__restrict__ 
           cont |= c ? (1u << k) : 0u;
         }
       }
-#if IA_HGB_QUAD
       uint32_t c_index[8];
       float c_v0[8], c_v1[8];
-#endif
 #pragma unroll
       for (int idx = 0; idx < 8; idx++) {
         const uint32_t cx = g[0] + (idx & 1), cy = g[1] + ((idx >> 1) & 1), cz = g[2] + ((idx >> 2) & 1);
@@ -1353,16 +1253,9 @@ __global__ __launch_bounds__(256) void k_hashgrid_bwd(const float *__restrict__ 
             if ((cont >> k) & 1u) { v0 += a0; v1 += a1; }
           }
         }
-#if IA_HGB_QUAD
         c_index[idx] = index;
         c_v0[idx] = (live && head) ? v0 : 0.f;   // zero = nothing to add (skipped below)
         c_v1[idx] = (live && head) ? v1 : 0.f;
-#else
-        if (live && head) {
-          if (v0 != 0.f) unsafeAtomicAdd(dtab + (size_t)index * 2, v0);
-          if (v1 != 0.f) unsafeAtomicAdd(dtab + (size_t)index * 2 + 1, v1);
-        }
-#endif
         if (dx && live) {
           union { uint32_t u; half2v h; } c;
           c.u = tab[index];
@@ -1373,7 +1266,6 @@ __global__ __launch_bounds__(256) void k_hashgrid_bwd(const float *__restrict__ 
           gx[2] += scale * wx * wy * sz * dot;
         }
       }
-#if IA_HGB_QUAD
       // ---- quad-cooperative scatter -----------------------------------------------------------------------------------
       // The atomic units take ~21 G REQUESTS/s whatever they carry, and the lanes of one instruction that hit adjacent
       // words are one request (tools/ubench/atomics.hip: 21 / 42 / 84 G atomics/s for single words / pairs / 16-byte
@@ -1396,7 +1288,6 @@ __global__ __launch_bounds__(256) void k_hashgrid_bwd(const float *__restrict__ 
           ia_hgb_quad_round<3>(dtab, qj, i0, i1, q0, q1, q2, q3);
         }
       }
-#endif
     }
     if (dx && live) {
 #pragma unroll

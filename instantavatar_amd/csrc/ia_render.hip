@@ -516,18 +516,14 @@ __global__ void k_fill_i32(int32_t *p, int32_t v, int n) {
 // `iters` jittered points of one cell are neighbours in the point list (same workgroup, adjacent
 // lanes): their solves start within one cell of each other and share transform-grid lines in L1.
 // Enumeration of the cells: probe p belongs to cell ia_probe_cell(p / iters) of the occupancy grid's own index [x][y][z] (z
-// fastest, raymarcher.cu:49-52).  IA_PROBE_ORDER_X = 0: in that order; 1: x fastest; 2: Morton.  The probe launch of the
+// fastest, raymarcher.cu:49-52).  Morton order for G = 64, x fastest otherwise.  The probe launch of the
 // search is bound by its vector-L1 miss path (hit rate 71 % against 92 % in the render launches, profiles/r04_pmc_search.json),
 // and which cells share a workgroup decides how many lines its lanes share.
 // Only the ORDER of the points changes: every cell keeps its jitter and its probes, the density is bit-identical.
-// Measured (profiles/r05_ab_probe.txt): x-fastest (1) +7 % on the probe launch, Morton (2) -2 %: a workgroup's 13 cells as a
-// compact block share the most 128-byte lines (simulated unique lines per live solve 2.37 -> 2.05).
-#ifndef IA_PROBE_ORDER_X
-#define IA_PROBE_ORDER_X 2
-#endif
+// A workgroup's 13 cells as a compact block share the most 128-byte lines (tools/variants/probe_order_r05.diff.txt).
+// Measured against the grid's own order (profiles/r05_ab_probe.txt): x fastest +7 % on the launch, Morton -2 % (unique lines per solve 2.37 -> 2.05).
 __device__ __forceinline__ int ia_probe_cell(int c, int G) {
-  if (IA_PROBE_ORDER_X == 0) return c;
-  if (IA_PROBE_ORDER_X == 2 && G == 64) {   // Morton: bits of c dealt to z, y, x in turn -> a workgroup's 13 cells form a compact block
+  if (G == 64) {   // Morton: bits of c dealt to z, y, x in turn -> a workgroup's 13 cells form a compact block
     int x = 0, y = 0, z = 0;
 #pragma unroll
     for (int b = 0; b < 6; b++) {
@@ -1188,10 +1184,7 @@ extern "C" int ia_render_test(const float *rays_o, const float *rays_d, const fl
     RenderState *st = rw.st + it;
     // upper bounds for the launches: iteration 0 may have R alive rays, later
     // ones never more than the first compaction leaves; keep R (idle waves exit).
-#ifndef IA_MARCH_LDS
-#define IA_MARCH_LDS 1
-#endif
-    if (IA_MARCH_LDS && G == 64 && ((size_t)occ_bits & 15) == 0)
+    if (G == 64 && ((size_t)occ_bits & 15) == 0)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_compact<true>), gR, blk, 0, s, rays_o, rays_d, rw.near_w, far, rw.step, cur, st, occ_bits,
                          G, aabb, rw.s_pts, rw.s_t, rw.ray_off, rw.ray_cnt, rw.counter, rw.sample_cap, max_samples, max_batch);
     else

@@ -236,10 +236,7 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
   // below writes for a workgroup without candidates (s_blockbase = 0, all prefix sums 0).  Four barriers and the filter's
   // and the compaction's LDS sweeps less; measured neutral on the launch time (profiles/r05_ab_probe.txt: those cycles are
   // waves waiting, not a resource the solver loops of the other waves compete for).
-#ifndef IA_SEARCH_EARLY_OUT
-#define IA_SEARCH_EARLY_OUT 1
-#endif
-  if (IA_SEARCH_EARLY_OUT && MODE != 0 && !any_root) {
+  if (MODE != 0 && !any_root) {
     if (tid < np) {
       pt_off[p0 + tid] = 0;
       pt_cnt[p0 + tid] = 0;

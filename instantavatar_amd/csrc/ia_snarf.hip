@@ -310,11 +310,9 @@ __global__ void k_bbox_init(float *bbox) {
   else if (threadIdx.x < 6) bbox[threadIdx.x] = __int_as_float(0xff800000);
 }
 
-#ifndef IA_PRE_LDS_STORE
-#define IA_PRE_LDS_STORE 1  // stage the channel-last transform records through LDS so that every store instruction is contiguous:
-                            // 25.8 -> 18.9 us for the product call (d + bbox, incl. the reduce launch), streams alone 19.7 -> 13.2 us
-                            // (profiles/r06_ab_precompute.txt)
-#endif
+// LDS_STORE stages the channel-last transform records through LDS so that every store instruction is contiguous: 25.8 -> 18.9 us
+// for the product call (d + bbox, incl. the reduce launch), streams alone 19.7 -> 13.2 us (profiles/r06_ab_precompute.txt).  It
+// needs whole waves; the direct stores (LDS_STORE = false) serve the grids that do not divide evenly.
 #ifndef IA_PRE_VPT
 #define IA_PRE_VPT 4  // consecutive voxels (along W) per thread: 1, 2 or 4 (measured 173 / 185 / 95 us)
 #endif
@@ -522,7 +520,7 @@ extern "C" int ia_precompute_ws(const float *voxel_w, const float *tfs, float *v
   }
   // (the LDS-staged stores need whole waves: every lane of a wave takes the same number of trips)
   const long n_thr = (long)grid->D * grid->H * grid->W / IA_PRE_VPT;
-  if (IA_PRE_LDS_STORE && n_thr % 64 == 0 && n_thr % ((long)blocks * 256) == 0)
+  if (n_thr % 64 == 0 && n_thr % ((long)blocks * 256) == 0)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_precompute<IA_PRE_VPT, true>), dim3(blocks), dim3(256), 0, s, voxel_w, tfs, voxel_J, voxel_d, bbox,
                        partial, ia_make_grid_dev(grid));
   else
