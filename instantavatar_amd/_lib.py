@@ -55,6 +55,9 @@ class SmplBody(C.Structure):
                 ("J0", C.c_void_p), ("JS", C.c_void_p), ("parents", C.c_void_p), ("n_verts", C.c_int)]
 
 HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip.h")
+# the sequence-ingest entry points (csrc/ia_io.hip) are declared in a header of their own, parsed into a table of its own
+# (`io_declarations`): `declarations()` / `EXPORTED` stay the main header's set
+IO_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_io.h")
 
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
@@ -112,20 +115,38 @@ def parse_header(text):
 
 
 _decls = None
+_io_decls = None
+
+
+def _parse_file(path):
+    try:
+        with open(path) as f:
+            text = f.read()
+    except OSError as e:
+        raise ImportError("instantavatar_amd: the C header %s is missing (%s); the binding is derived from it"
+                          % (os.path.normpath(path), e))
+    return parse_header(text)
 
 
 def declarations():
     """parse_header of this checkout's header, read once."""
     global _decls
     if _decls is None:
-        try:
-            with open(HEADER_PATH) as f:
-                text = f.read()
-        except OSError as e:
-            raise ImportError("instantavatar_amd: the C header %s is missing (%s); the binding is derived from it"
-                              % (os.path.normpath(HEADER_PATH), e))
-        _decls = parse_header(text)
+        _decls = _parse_file(HEADER_PATH)
     return _decls
+
+
+def io_declarations():
+    """parse_header of include/instantavatar_hip_io.h, read once: bound in `lib()` next to the main table and reachable
+    through `call`; its names are disjoint from the main header's."""
+    global _io_decls
+    if _io_decls is None:
+        d = _parse_file(IO_HEADER_PATH)
+        both = sorted(set(d) & set(declarations()))
+        if both:
+            raise ImportError("instantavatar_hip_io.h declares %s, which instantavatar_hip.h declares already" % ", ".join(both))
+        _io_decls = d
+    return _io_decls
 
 
 def __getattr__(name):
@@ -165,7 +186,7 @@ def lib():
                     "instantavatar_amd: %s was built from other sources than this checkout (differs in: %s). Rebuild it "
                     "(`python -m instantavatar_amd.build`), or set IA_ALLOW_STALE_LIB=1 to run it anyway." % (LIB_PATH, ", ".join(diff)))
         l = C.CDLL(LIB_PATH)
-        for name, d in declarations().items():
+        for name, d in list(declarations().items()) + list(io_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -253,7 +274,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

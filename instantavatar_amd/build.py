@@ -2,7 +2,7 @@
 sources, so the .so travels to the GPU box with the repo snapshot).
 
 The library carries a MANIFEST of what it was built from, two 16-hex-digit hashes per translation unit:
-  * source hash over (compiler flags, the two shared headers, local includes, the source file) -- `needs_build()`
+  * source hash over (compiler flags, the shared headers, local includes, the source file) -- `needs_build()`
     compares it with the checkout as it is now (not file times: a prebuilt library that is newer than an edited
     checkout used to win);
   * device-code hash = sha256 of the object's `.hip_fatbin` section (the gfx950 code objects) -- `bench.py` accepts a
@@ -22,7 +22,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libinstantavatar_hip.so")
-SOURCES = ["ia_error.cpp", "ia_snarf.hip", "ia_search.hip", "ia_field.hip", "ia_render.hip", "ia_prof.hip", "ia_voxelise.hip", "ia_loss.hip", "ia_smpl_nn.hip", "ia_data.hip", "ia_mesh.hip", "ia_optim.hip", "ia_smpl_lbs.hip"]
+SOURCES = ["ia_error.cpp", "ia_snarf.hip", "ia_search.hip", "ia_field.hip", "ia_render.hip", "ia_prof.hip", "ia_voxelise.hip", "ia_loss.hip", "ia_smpl_nn.hip", "ia_data.hip", "ia_mesh.hip", "ia_optim.hip", "ia_smpl_lbs.hip", "ia_io.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: fused multiply-adds appear only where the sources spell them
 # (IA_DOT3 / __builtin_fmaf), the same sequence the CPU checker uses
@@ -35,7 +35,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # parity tests are bit-exact with it): 193.4 -> 191.7 us on a frame's sample points (profiles/r04_ab_search_variants.txt)
 TU_FLAGS = {"ia_search.hip": ["-fno-slp-vectorize"]}
 OBJCOPY = os.environ.get("LLVM_OBJCOPY", "/opt/rocm/lib/llvm/bin/llvm-objcopy")
-SHARED_HEADERS = [os.path.join(CSRC, "ia_common.h"), os.path.join(HERE, "..", "include", "instantavatar_hip.h")]
+SHARED_HEADERS = [os.path.join(CSRC, "ia_common.h"), os.path.join(HERE, "..", "include", "instantavatar_hip.h"),
+                  os.path.join(HERE, "..", "include", "instantavatar_hip_io.h")]
 _MARK = b"IA_SOURCE_MANIFEST="
 
 

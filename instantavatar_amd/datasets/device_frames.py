@@ -4,10 +4,16 @@ camera rays (:12-25), masked compositing with a random background (:107-115), th
 (:141-150) -- with the frames resident in HBM and every step a handful of kernels.  At ~1.2 ms per training step the
 host loader would be the bottleneck.
 
-Image decoding and resizing (cv2.imread / cv2.resize, :100-105) stay on the host: they happen once, when the frames
-are uploaded by `DeviceFrames.from_arrays`.
+Image decoding and resizing (cv2.imread / cv2.resize, :100-105) happen once per sequence, in
+`DeviceFrames.from_directory`: the files of a sequence directory (datasets/sequence_dir.py) are decoded with PIL on host
+threads, staged chunk by chunk through pinned memory, and resized by `ia_io_ingest_chunk` (csrc/ia_io.hip) straight into
+the resident stores -- the full-resolution sequence is never resident, on the device or on the host.  The factor-2
+resize rule is PARITY UNPINNED against OpenCV itself (no cv2 to compare with); see sequence_dir.py.  `DeviceFrames.from_arrays` still takes arrays that are already decoded and at the training resolution.
 """
+import concurrent.futures
 import ctypes as C
+import os
+import time
 
 import numpy as np
 import torch
@@ -29,6 +35,42 @@ def make_rays(K, c2w, H, W, device):
     _lib.require_cuda(o)
     _lib.call("ia_make_rays", dp(Kinv), dp(R), dp(t), H, W, o, d)
     return o, d
+
+
+_MASK_FORMS = {"peoplesnapshot": 1, "custom": 2}     # IA_IO_MASK_U8 / IA_IO_MASK_GREY (include/instantavatar_hip_io.h)
+
+
+def _decode_image(path, out):
+    """cv2.imread(path) into out uint8 [H0, W0, 3]: three channels B, G, R, an alpha channel dropped, grey replicated"""
+    from PIL import Image
+    from .sequence_dir import SequenceError
+    with Image.open(path) as im:
+        if im.mode not in ("RGB", "RGBA", "L", "P"):
+            raise SequenceError("%s: PNG mode %s (more than 8 bits per channel?) is not read here; cv2.imread would convert it" % (path, im.mode))
+        a = np.asarray(im.convert("RGB"))
+    if a.shape != out.shape:
+        raise SequenceError("%s is %d x %d, expected %d x %d" % (path, a.shape[0], a.shape[1], out.shape[0], out.shape[1]))
+    out[...] = a[..., ::-1]
+
+
+def _decode_mask(path, out, kind):
+    """the mask file's bytes into out uint8 [H0, W0]: np.load (peoplesnapshot.py:101) or cv2.imread(path, IMREAD_GRAYSCALE)
+    (custom.py:99; its `/ 255` is the kernel's)"""
+    from .sequence_dir import SequenceError
+    if kind == "peoplesnapshot":
+        a = np.load(path)
+        if a.dtype != np.uint8:
+            raise SequenceError("%s: a %s mask; the reference's preprocessing writes uint8 0/1 arrays, and cv2.resize of another "
+                                "type follows another rule" % (path, a.dtype))
+    else:
+        from PIL import Image
+        with Image.open(path) as im:
+            if im.mode != "L":
+                raise SequenceError("%s: PNG mode %s; a mask is an 8-bit grey image (cv2's colour -> grey conversion is not restated)" % (path, im.mode))
+            a = np.asarray(im)
+    if a.shape != out.shape:
+        raise SequenceError("%s has shape %s, expected %s" % (path, a.shape, out.shape))
+    out[...] = a
 
 
 class DeviceFrames:
@@ -61,6 +103,60 @@ class DeviceFrames:
     def from_arrays(cls, images_u8, masks, K, c2w, smpl_params, sampler, device, **kw):
         return cls(torch.as_tensor(np.ascontiguousarray(images_u8), device=device), torch.as_tensor(np.ascontiguousarray(masks, np.float32), device=device),
                    K, c2w, smpl_params, sampler, **kw)
+
+    @classmethod
+    def from_directory(cls, seq, sampler, device, chunk=None, workers=None, log=None):
+        """The frames of `seq` (sequence_dir.read_sequence) decoded, resized by seq.downscale and resident on `device`.
+        chunk: frames per staged chunk (default: about 32 MB of full-resolution pixels); workers: decoding threads, at most
+        min(16, os.cpu_count()); log: a callable that is handed the one-line report of the load (frames, seconds, MB/s decoded).
+        Three stages overlap on consecutive chunks: PIL decodes chunk k + 1 into one pinned buffer while the side stream
+        copies chunk k from the other and `ia_io_ingest_chunk` writes its frames into the stores."""
+        from .sequence_dir import resize_rule
+        factor = resize_rule(seq.H0, seq.W0, seq.downscale)
+        if (seq.H, seq.W) != (seq.H0 // factor, seq.W0 // factor):
+            raise ValueError("sequence: training size %d x %d is not the source size %d x %d over %d" % (seq.H, seq.W, seq.H0, seq.W0, factor))
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.IAError("DeviceFrames.from_directory needs a GPU device (got %s); there is no CPU path" % device)
+        N, H0, W0, H, W = len(seq.image_files), seq.H0, seq.W0, seq.H, seq.W
+        px = H0 * W0
+        chunk = max(1, min(N, int(chunk) if chunk else (32 << 20) // (px * 4) or 1))
+        workers = max(1, min(16, os.cpu_count() or 1, int(workers) if workers else 16))
+        form = _MASK_FORMS[seq.kind]
+        t0 = time.perf_counter()
+        with torch.cuda.device(device):
+            images = torch.empty((N, H, W, 3), dtype=torch.uint8, device=device)
+            masks = torch.empty((N, H, W), dtype=torch.float32, device=device)
+            # per slot: [chunk, H0, W0, 3] image bytes followed by [chunk, H0, W0] mask bytes -- one copy per chunk
+            host = [torch.empty(chunk * px * 4, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            dev = [torch.empty(chunk * px * 4, dtype=torch.uint8, device=device) for _ in range(2)]
+            copied = [None, None]         # per slot: the event after the last copy out of its pinned buffer
+            side = torch.cuda.Stream(device)
+            with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
+                for k, first in enumerate(range(0, N, chunk)):
+                    n, slot = min(chunk, N - first), k % 2
+                    if copied[slot] is not None:
+                        copied[slot].synchronize()      # the pinned buffer is free again (chunk k - 2 has left it)
+                    h = host[slot].numpy()
+                    h_img, h_msk = h[:chunk * px * 3].reshape(chunk, H0, W0, 3), h[chunk * px * 3:].reshape(chunk, H0, W0)
+                    jobs = [pool.submit(_decode_image, seq.image_files[first + i], h_img[i]) for i in range(n)]
+                    jobs += [pool.submit(_decode_mask, seq.mask_files[first + i], h_msk[i], seq.kind) for i in range(n)]
+                    for j in jobs:
+                        j.result()
+                    with torch.cuda.stream(side):
+                        # (the device staging buffer of the slot is reused in stream order behind chunk k - 2's kernel)
+                        dev[slot].copy_(host[slot], non_blocking=True)
+                        copied[slot] = torch.cuda.Event()
+                        copied[slot].record(side)
+                        d = dev[slot]
+                        _lib.call("ia_io_ingest_chunk", d[:chunk * px * 3], d[chunk * px * 3:], form, n, H0, W0, factor, images, masks, first, N)
+            side.synchronize()
+        dt = time.perf_counter() - t0
+        if log is not None:
+            mb = N * px * 4 / 1e6
+            log("loaded %d frames %dx%d -> %dx%d (%s, downscale %d) in %.2f s: %.1f MB/s decoded, %d decoding threads, chunks of %d" % (
+                N, W0, H0, W, H, seq.kind, factor, dt, mb / max(dt, 1e-9), workers, chunk))
+        return cls(images, masks, seq.K, seq.c2w, seq.smpl_params, sampler, near=seq.near, far=seq.far)
 
     def __len__(self):
         return self.N

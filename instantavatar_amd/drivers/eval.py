@@ -4,6 +4,12 @@ the test frames with the refined parameters, write `test/<i>.png` = [ground trut
 PSNR / SSIM / LPIPS(alex) on the written 8-bit images -> `results.txt`.
 
     python -m instantavatar_amd.drivers.eval --synthetic --frames 4 --res 128 --epochs 2 --out /tmp/eval
+    python -m instantavatar_amd.drivers.eval --data ./data/PeopleSnapshot/male-3-casual --dataset peoplesnapshot --start 456 --end 675 --skip 4 \
+        --downscale 2 --smpl-dir ./data/SMPLX/smpl --gender male --ckpt checkpoints/last.ckpt --out /tmp/eval
+
+`--data DIR`: the TEST split of a sequence directory in the reference's layout (datasets/sequence_dir.py; the split options as
+numbers or from `--dataset-conf`), read with `refine` set -- a PeopleSnapshot directory then takes its SMPL parameters from
+`poses/anim_nerf_test.npz` (peoplesnapshot.py:62-64) -- and handed to the same refinement, rendering and metrics.
 
 `--synthetic`: the subject is the synthetic SMPL-like body + field; the "test images" are its renderings at the true poses,
 the checkpoint under evaluation has the same field, and its SMPL tables start `--pose-noise` rad / `--transl-noise` m off
@@ -96,8 +102,15 @@ def render_test_images(model, frames, out_dir):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--synthetic", action="store_true", required=True,
+    ap.add_argument("--synthetic", action="store_true",
                     help="synthetic SMPL-like body and test frames (the only data source shipped with this package)")
+    from .sequence_args import add_data_arguments
+    add_data_arguments(ap)
+    ap.add_argument("--smpl-dir", default="./data/SMPLX/smpl")
+    ap.add_argument("--gender", default="neutral")
+    ap.add_argument("--synthetic-body", action="store_true", help="--data: the synthetic SMPL-like body instead of a SMPL pickle from --smpl-dir")
+    ap.add_argument("--confs", default=os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "confs"))
+    ap.add_argument("--deformer", default="fast_snarf")
     ap.add_argument("--ckpt", help="Lightning-layout checkpoint of the field to evaluate (default: the synthetic field itself)")
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--res", type=int, default=256)
@@ -110,6 +123,8 @@ def main(argv=None):
     ap.add_argument("--lpips-trunk", help="a saved torchvision alexnet().features.state_dict()")
     ap.add_argument("--out", default="eval_out")
     args = ap.parse_args(argv)
+    if bool(args.synthetic) == bool(args.data):
+        ap.error("exactly one of --synthetic / --data <dir> is required")
     from .launch import Launch
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # the refinement steps ONE optimiser over the test frames in sequence (eval.py:70-97) and the metrics are means over
@@ -117,12 +132,22 @@ def main(argv=None):
         raise SystemExit("eval: a single-process driver (start it without torch.distributed.run)")
     device = Launch.from_env(who="eval").device     # cuda:LOCAL_RANK
     torch.manual_seed(42)
-    teacher, _, _ = build_synthetic_model(device)
-    model, _, _ = build_synthetic_model(device)
+    if args.data:
+        # the datamodule's testset (eval.py:42-46 with SNARF_NGP_refine.yaml: sampler=edge, optimize_SMPL.is_refine) + DNeRFModel
+        from . import config as cfg
+        from .sequence_args import load_directory
+        from .train import build_frames_model
+        frames = load_directory(args, "test", cfg.instantiate(cfg.load_group(args.confs, "sampler", "edge", {})), device, refine=True)
+        model = build_frames_model(args, frames, device)
+        start = {k: v.detach().cpu().numpy().copy() for k, v in frames.smpl_params.items()}
+    else:
+        teacher, _, _ = build_synthetic_model(device)
+        model, _, _ = build_synthetic_model(device)
     if args.ckpt:
         missing, unexpected = ckpt_io.load_checkpoint(model, args.ckpt, map_location=device, skip_prefixes=("SMPL_param",), strict_self_check=True)
         print("checkpoint %s loaded (step %d), SMPL_param entries skipped" % (args.ckpt, model.global_step))
-    frames, true, start = synthetic_test_set(device, teacher, args.res, args.frames, args.pose_noise, args.transl_noise)
+    if not args.data:
+        frames, true, start = synthetic_test_set(device, teacher, args.res, args.frames, args.pose_noise, args.transl_noise)
     from ..models.structures.body_model_param import SMPLParamEmbedding
     model.SMPL_param = SMPLParamEmbedding(**{k: torch.as_tensor(v.copy()) for k, v in start.items()}).to(device)
     field_before = [p.detach().clone() for n, p in model.named_parameters() if not n.startswith("SMPL_param")]
@@ -133,7 +158,10 @@ def main(argv=None):
     moved = {k: float((getattr(model.SMPL_param, k).weight.detach().cpu() - torch.as_tensor(start[k])).abs().max()) for k in ("body_pose", "global_orient", "transl")}
     print("refined %d frames in %d steps (field parameters untouched); largest change of the tables: %s" % (len(frames), steps, moved))
     if max(moved.values()) == 0.0:
-        raise RuntimeError("eval: the SMPL tables did not move -- no gradient reached them")
+        if not args.data:
+            raise RuntimeError("eval: the SMPL tables did not move -- no gradient reached them")
+        # (a real sequence can legitimately end here: a field whose occupancy grid is empty renders nothing to refine against)
+        print("warning: the SMPL tables did not move -- no gradient reached them (an untrained field?)")
     test_dir = os.path.join(args.out, "test")
     n = render_test_images(model, frames, test_dir)
     lp = None

@@ -4,6 +4,11 @@ the `SMPLDeformer` plugin (deformer=smpl), on patch batches (sampler=patch) with
 parameters to `<out>/poses/train.npz` for the train stage.
 
     python -m instantavatar_amd.drivers.fit --synthetic --steps 200 --out /tmp/seq
+    python -m instantavatar_amd.drivers.fit --data ./data/custom/seq --dataset custom --start 0 --end 99 --downscale 2 \
+        --smpl-dir ./data/SMPLX/smpl --steps 3000 --out ./data/custom/seq
+
+`--data DIR` reads a sequence directory in the reference's layout (datasets/sequence_dir.py) with `fitting` set: the custom
+layout then starts from `poses_optimized.npz` (custom.py:67-76), the PeopleSnapshot layout from its usual pose files.
 
 `fit_sequence(...)` takes any `DeviceFrames` (instantavatar_amd/datasets/device_frames.py); `--synthetic` builds one
 from the synthetic avatar with perturbed initial poses (no dataset ships with this package).  The LPIPS term of the
@@ -122,26 +127,34 @@ def main(argv=None):
     ap.add_argument("--synthetic", action="store_true", help="frames rendered from the synthetic avatar, perturbed initial SMPL parameters")
     ap.add_argument("--frames", help="npz of a pre-decoded sequence (drivers.train --frames: images uint8 [N,H,W,3], masks, K, (c2w), betas, "
                                      "global_orient, body_pose, transl = the initial SMPL parameters, e.g. the output of a pose estimator)")
+    from .sequence_args import add_data_arguments
+    add_data_arguments(ap)
     ap.add_argument("--smpl-dir", default="./data/SMPLX/smpl")
     ap.add_argument("--gender", default="neutral")
-    ap.add_argument("--synthetic-body", action="store_true", help="--frames: the synthetic SMPL-like body instead of a SMPL pickle from --smpl-dir")
+    ap.add_argument("--synthetic-body", action="store_true", help="--frames / --data: the synthetic SMPL-like body instead of a SMPL pickle from --smpl-dir")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--out", default="outputs/fit")
     args = ap.parse_args(argv)
-    if bool(args.synthetic) == bool(args.frames):
-        ap.error("exactly one of --synthetic / --frames <npz> is required")
+    if bool(args.synthetic) + bool(args.frames) + bool(args.data) != 1:
+        ap.error("exactly one of --synthetic / --frames <npz> / --data <dir> is required")
     from .launch import Launch
     launch = Launch.from_env(who="fit")
     try:
         device = launch.device
-        if args.frames:
-            # confs/SNARF_NGP_fitting.yaml: deformer=smpl, sampler=patch -- the sequence from pre-decoded arrays (see drivers/train.py)
+        if args.frames or args.data:
+            # confs/SNARF_NGP_fitting.yaml: deformer=smpl, sampler=patch -- the sequence from pre-decoded arrays or from a
+            # sequence directory (see drivers/train.py)
             from . import config as cfg
+            from .sequence_args import load_directory
             from .train import load_frames
             from ..deformers.smplx import _abs_smpl
             confs = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "confs")
-            frames = load_frames(args.frames, cfg.instantiate(cfg.load_group(confs, "sampler", "patch", {})), device)
+            sampler = cfg.instantiate(cfg.load_group(confs, "sampler", "patch", {}))
+            if args.data:
+                frames = load_directory(args, "train", sampler, device, say=print if launch.is_main else (lambda *a, **k: None), fitting=True)
+            else:
+                frames = load_frames(args.frames, sampler, device)
             body_model = (SMPL.from_dict(synthetic.make_body()) if args.synthetic_body else SMPL(_abs_smpl(args.smpl_dir), gender=args.gender)).to(device)
         else:
             frames, body_model, _ = synthetic_frames(device, res=args.res)

@@ -8,9 +8,15 @@ PRE-DECODED sequence -- the arrays peoplesnapshot.py:99-151 reads per item from 
 (as cv2.imread returns them, at the training resolution), `masks` [N,H,W], `K` [3,3], optional `c2w` [4,4], and the SMPL
 parameters of poses/anim_nerf_train.npz (`betas` [1,10], `global_orient` [N,3], `body_pose` [N,69], `transl` [N,3]) -- through
 datasets.DeviceFrames and the confs/sampler group, with the plugins built from confs/ like the reference's Hydra run.
+`--data DIR --dataset {peoplesnapshot,custom}` trains on a SEQUENCE DIRECTORY in the reference's layout (datasets/sequence_dir.py:
+cameras.npz, images/, masks/, poses...): the train and val splits are read, decoded and resized onto the device by
+`DeviceFrames.from_directory`; the split options are given as numbers (`--start/--end/--skip/--downscale/--near/--far`, the val
+split being the one frame `--val-frame`) or taken from a reference dataset config (`--dataset-conf confs/dataset/.../x.yaml`).
 
     python -m instantavatar_amd.drivers.train --synthetic --steps 200 --ckpt /tmp/avatar/last.ckpt
     python -m instantavatar_amd.drivers.train --frames seq.npz --smpl-dir ./data/SMPLX/smpl --gender male --sampler patch --steps 3000
+    python -m instantavatar_amd.drivers.train --data ./data/PeopleSnapshot/male-3-casual --dataset peoplesnapshot --start 0 --end 455 --skip 4 \
+        --downscale 2 --val-frame 456 --smpl-dir ./data/SMPLX/smpl --gender male --steps 3000
 """
 import argparse
 import os
@@ -23,6 +29,7 @@ from .. import synthetic
 from ..pipeline import build_synthetic_model, make_batch
 from ..training import GraphedTrainStep, NeRFLoss, configure_optimizer, configure_scheduler
 from . import checkpoint as ckpt_io
+from .sequence_args import add_data_arguments, load_directory
 
 
 def synthetic_batches(device, teacher, res=256, n_frames=8, n_rays=4096, seed=1234, rank=0, world_size=1):
@@ -82,6 +89,22 @@ def load_frames(path, sampler, device):
     return DeviceFrames.from_arrays(imgs, masks, z["K"], c2w, smpl, sampler, device)
 
 
+def build_frames_model(args, frames, device):
+    """DNeRFModel.__init__ from the conf groups (DNeRF.py:22-28) for a sequence's frames"""
+    from . import config as cfg
+    from ..pipeline import AvatarModel
+    kw = dict(model_path=args.smpl_dir)
+    if args.synthetic_body:
+        from ..deformers.smplx import SMPL
+        kw = dict(body_model=SMPL.from_dict(synthetic.make_body()).to(device))
+    deformer, net, renderer = cfg.build_plugins(args.confs, args.deformer, gender=args.gender, deformer_kwargs=kw)
+    model = AvatarModel(deformer, net, renderer).to(device)
+    renderer.initialize(len(frames))
+    deformer.initialize(frames.smpl_params["betas"][:1], device)
+    deformer.initialized = True
+    return model
+
+
 def synthetic_val_batch(device, teacher, res=256, frame=0):
     """A whole frame with its target image: what the "val" split's __getitem__ yields (peoplesnapshot.py:112-125)."""
     poses, tr = synthetic.procedural_pose_track(8)
@@ -137,7 +160,9 @@ def main(argv=None):
                     help="synthetic SMPL-like body and targets (the only data source shipped with this package)")
     ap.add_argument("--frames", help="npz of a pre-decoded sequence: images uint8 [N,H,W,3], masks [N,H,W], K [3,3], (c2w [4,4]), betas, "
                                      "global_orient, body_pose, transl (see the module docstring)")
-    ap.add_argument("--sampler", default="patch", help="confs/sampler group for --frames: patch (SNARF_NGP.yaml) or edge (SNARF_NGP_refine.yaml)")
+    add_data_arguments(ap)
+    ap.add_argument("--val-frame", type=int, help="--data: the file the val split consists of (default: --start)")
+    ap.add_argument("--sampler", default="patch", help="confs/sampler group for --frames / --data: patch (SNARF_NGP.yaml) or edge (SNARF_NGP_refine.yaml)")
     ap.add_argument("--smpl-dir", default="./data/SMPLX/smpl")
     ap.add_argument("--gender", default="neutral")
     ap.add_argument("--synthetic-body", action="store_true", help="--frames: the synthetic SMPL-like body instead of a SMPL pickle from --smpl-dir")
@@ -152,8 +177,8 @@ def main(argv=None):
     ap.add_argument("--check-val-every-n-epoch", type=int, default=10,
                     help="confs/SNARF_NGP.yaml train.check_val_every_n_epoch: a validation_step and ONE step of the LR schedule every that many epochs")
     args = ap.parse_args(argv)
-    if bool(args.synthetic) == bool(args.frames):
-        ap.error("exactly one of --synthetic / --frames <npz> is required")
+    if bool(args.synthetic) + bool(args.frames) + bool(args.data) != 1:
+        ap.error("exactly one of --synthetic / --frames <npz> / --data <dir> is required")
     from .launch import Launch
     launch = Launch.from_env(who="train")
     try:
@@ -166,26 +191,21 @@ def _run(args, launch):
     """train.py:27-41 for rank `launch.rank` of `launch.world_size` (the reference is `pl.Trainer(gpus=1)`, train.py:29-30)."""
     device, world, main = launch.device, launch.world_size, launch.is_main
     say = print if main else (lambda *a, **k: None)
-    frames = None
-    if args.frames:
+    frames = val_frames = None
+    if args.frames or args.data:
         # DNeRFModel.__init__ from the conf groups (DNeRF.py:22-28) + the datamodule's trainset as device-resident frames
         from . import config as cfg
-        from ..pipeline import AvatarModel
         sampler = cfg.instantiate(cfg.load_group(args.confs, "sampler", args.sampler, {}))
-        frames = load_frames(args.frames, sampler, device)
-        kw = dict(model_path=args.smpl_dir)
-        if args.synthetic_body:
-            from ..deformers.smplx import SMPL
-            kw = dict(body_model=SMPL.from_dict(synthetic.make_body()).to(device))
-        deformer, net, renderer = cfg.build_plugins(args.confs, args.deformer, gender=args.gender, deformer_kwargs=kw)
-        model = AvatarModel(deformer, net, renderer).to(device)
-        renderer.initialize(len(frames))
-        deformer.initialize(frames.smpl_params["betas"][:1], device)
-        deformer.initialized = True
+        if args.data:
+            frames = load_directory(args, "train", sampler, device, say=say)
+            val_frames = load_directory(args, "val", None, device, say=say, frame=args.val_frame if args.val_frame is not None else args.start)
+        else:
+            frames = load_frames(args.frames, sampler, device)
+        model = build_frames_model(args, frames, device)
         args.res = frames.H
         args.steps_per_epoch = len(frames)
         teacher = None
-        say("%d frames %dx%d from %s, sampler %s" % (len(frames), frames.W, frames.H, args.frames, type(sampler).__name__))
+        say("%d frames %dx%d from %s, sampler %s" % (len(frames), frames.W, frames.H, args.frames or args.data, type(sampler).__name__))
     else:
         teacher, _, _ = build_synthetic_model(device)
         model, _, _ = build_synthetic_model(device)
@@ -198,7 +218,7 @@ def _run(args, launch):
         ckpt_io.load_checkpoint(model, args.ckpt, map_location=device, optimizer=opt, scheduler=sched)
         say("resumed from %s at step %d (lr %.2e)" % (args.ckpt, model.global_step, float(opt.param_groups[0]["lr"])))
     from ..evaluation import validation_step
-    val_batch = frames.frame(0) if frames is not None else synthetic_val_batch(device, teacher, res=args.res)
+    val_batch = (val_frames or frames).frame(0) if frames is not None else synthetic_val_batch(device, teacher, res=args.res)
     val_size = (frames.H, frames.W) if frames is not None else (args.res, args.res)
 
     def validate(m):
