@@ -265,6 +265,11 @@ class SMPLDeformer():
         from ..models.networks.ngp import NeRFNGPNet
         return isinstance(model, NeRFNGPNet)
 
+    def surface_normals(self, rays_o, rays_d, depth, alpha, net):
+        """Normal maps need the canonical roots and the blended transforms of the SNARF deformer; not built for this one."""
+        raise NotImplementedError("surface normals are implemented for the SNARF deformer (deformers.snarf_deformer.SNARFDeformer) "
+                                  "only; SMPLDeformer has no normal pass")
+
     def deform_test(self, pts, model):
         """smpl_deformer.py:122-131: invalid points -> rgb 0, sigma 0"""
         if self._native(model) and not torch.is_grad_enabled():

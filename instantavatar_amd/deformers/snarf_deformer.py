@@ -16,6 +16,7 @@ structure, snarf_deformer.py:127-159) for any other callable.
 """
 import os
 
+import numpy as np
 import torch
 
 from . import _opt
@@ -341,6 +342,57 @@ class SNARFDeformer():
         _lib.call("ia_deform_query", pts, P, None, self.deformer.voxel_J_cl, tfs, self.deformer._bones_c, k, self.deformer.grid_desc(),
                   net.field_desc(P * k), rgb, sigma, dmax, ws, ws.numel())
         return rgb, sigma
+
+    @torch.no_grad()
+    def surface_normals(self, rays_o, rays_d, depth, alpha, net, want_roots=False):
+        """Normal map of the posed density field for a rendered frame ("surface normals"): rays [R,3] in
+        the frame the marcher works in (after `transform_rays_w2s`), depth / alpha [R] as the renderer returned them ->
+        [R,3] fp32 in the camera frame: unit length where the pixel has alpha >= 0.5 and a valid canonical root, zero
+        elsewhere.  Seven launches behind the frame, no host synchronisation: surface points (compaction in ray order) ->
+        candidate search -> sigma and d sigma / d x_c of every candidate in one kernel -> arg-max -> n = -M^{-T} g, rotated back
+        with w2s.  The deformer must be prepared for the frame (`prepare_deformer`).
+        want_roots: also return copies of what the map was made from -- dict(n [1] the number of surface points, ray [R] their
+        rays, root [R,3] / grad [R,3] the winning canonical root and d sigma / d x_c of every point (zeros: no valid candidate)).
+        Scratch: sized for the worst case, every pixel a surface point with all k candidates valid -- 28 R k + 44 R bytes, cached
+        on the deformer (99 MB at 512^2 with 13 init bones); fixed pointers are what lets the pass be captured in a graph, and a
+        smaller candidate capacity would drop candidates silently when a frame exceeds it."""
+        _lib.require_cuda(rays_o, rays_d, depth, alpha)
+        f32 = lambda t, *shape: t.detach().reshape(*shape).float().contiguous()
+        o, d, dep, alp = f32(rays_o, -1, 3), f32(rays_d, -1, 3), f32(depth, -1), f32(alpha, -1)
+        R = o.shape[0]
+        dev = o.device
+        k = len(self.deformer.init_bones)
+        cap = R * k
+        # one scratch block for everything between the frame and the map (sized on first use: a captured graph keeps its pointers)
+        al = lambda n: (int(n) + 255) // 256 * 256
+        ws_bytes = int(_lib.call("ia_surface_points_workspace_bytes", R))
+        sizes = dict(ws=al(ws_bytes), n=256, pts=al(R * 12), ray=al(R * 4), off=al(R * 4), cnt=al(R), xc=al(cap * 12), sig=al(cap * 4),
+                     grad=al(cap * 12), root=al(R * 12), g=al(R * 12))
+        buf = _lib.scratch(self, "_ws_normals", sum(sizes.values()), dev)
+        part, at = {}, 0
+        for name, n in sizes.items():
+            part[name] = buf[at:at + n]
+            at += n
+        i32 = lambda name, n: part[name].view(torch.int32)[:n]
+        flt = lambda name, *shape: part[name].view(torch.float32)[:int(np.prod(shape))].view(*shape)
+        counts = i32("n", 2)      # [points, candidates]
+        pts, ray = flt("pts", R, 3), i32("ray", R)
+        _lib.call("ia_surface_points", o, d, dep, alp, R, pts, ray, counts[0:1], part["ws"], ws_bytes)
+        pt_off, pt_cnt, cand_xc = i32("off", R), part["cnt"][:R], flt("xc", cap, 3)
+        tfs = self.tfs.detach().float().contiguous()
+        _lib.call("ia_snarf_search_compact", pts, R, counts[0:1], self.deformer.voxel_J_cl, tfs, self.deformer._bones_c, k,
+                  self.deformer.grid_desc(), 1e-5, 1e-1, cand_xc, cap, pt_off, pt_cnt, counts[1:2], 1)
+        sig, grad = flt("sig", cap), flt("grad", cap, 3)
+        _lib.call("ia_field_sigma_grad", cand_xc, cap, counts[1:2], net.field_desc(), sig, grad)
+        root, g = flt("root", R, 3), flt("g", R, 3)
+        _lib.call("ia_candidate_select", sig, cand_xc, grad, cap, pt_off, pt_cnt, R, counts[0:1], root, g, None)
+        normals = torch.empty((R, 3), device=dev)
+        w2s = self.w2s.detach().reshape(4, 4).float().contiguous()
+        _lib.call("ia_normals_from_gradient", root, g, ray, R, counts[0:1], self.deformer.voxel_J_cl, self.deformer.grid_desc(), w2s, R,
+                  normals)
+        if want_roots:
+            return normals, dict(n=counts[0:1].clone(), ray=ray.clone(), root=root.clone(), grad=g.clone())
+        return normals
 
     def search_compact(self, pts, n_pts_dev=None, cap=None, want_J_inv=False, n_cand_out=None):
         """Search + filter + compaction (`ia_snarf_search_compact`): returns a dict with

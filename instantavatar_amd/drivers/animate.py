@@ -143,6 +143,30 @@ def pack_rgba8(out, dst):
     _lib.call("ia_pack_rgba8", rgb, alpha, alpha.numel(), dst)
 
 
+def pack_normals8(out, rays_d, dst_normal, dst_shaded, light=None):
+    """the normal map of a frame rendered with normals=True (`out[4]`) -> two uint8 [H,W,4] images on the device in ONE launch
+    (`ia_pack_normals8`): ((n + 1) / 2, covered) and (s, s, s, covered), s = max(0, n . l); l = `light` (device float [3]) or the
+    direction towards the camera along every pixel's own ray (-rays_d, the camera-frame directions of the sequence)."""
+    from .. import _lib
+    nrm = out[4]
+    _lib.require_cuda(nrm, rays_d, dst_normal, dst_shaded)
+    _lib.call("ia_pack_normals8", nrm, rays_d, light, nrm.numel() // 3, dst_normal, dst_shaded)
+
+
+def write_normal_frames(normal, shaded, out_dir, indices, workers=8):
+    """8-bit [n,H,W,4] normal / shaded images -> `normal_<i>.png`, `shaded_<i>.png`.  The channels are written as they are:
+    red / green / blue = x / y / z of (n + 1) / 2 in the camera frame (x right, y down, z away from the camera), alpha = covered."""
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    jobs = [("normal_%d.png" % i, f) for i, f in zip(indices, normal)] + [("shaded_%d.png" % i, f) for i, f in zip(indices, shaded)]
+
+    def one(job):
+        Image.fromarray(np.ascontiguousarray(job[1]), "RGBA").save(os.path.join(out_dir, job[0]))
+    with ThreadPoolExecutor(max_workers=max(1, workers)) as ex:
+        list(ex.map(one, jobs))
+
+
 def fixed_jitter(seed, device, iters=5, G=64):
     """One occupancy-probe jitter for the whole sequence (density_grid.py:98 draws a fresh torch.rand per frame): with it a
     frame is a function of its pose alone, so a sequence rendered by 1, 2 or 8 ranks gives the same files."""
@@ -150,13 +174,13 @@ def fixed_jitter(seed, device, iters=5, G=64):
     return torch.rand((iters, G * G * G, 3), generator=g).to(device)
 
 
-def _make_renderer(model, first, size, in_flight, probes, jitter):
+def _make_renderer(model, first, size, in_flight, probes, jitter, normals=False):
     from ..pipeline import PipelinedRenderer
-    return PipelinedRenderer(model, first, size, n_in_flight=in_flight, margin=1, probe_batches=probes, jitter=jitter)
+    return PipelinedRenderer(model, first, size, n_in_flight=in_flight, margin=1, probe_batches=probes, jitter=jitter, normals=normals)
 
 
 def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_flight=3, jitter=None, make_renderer=None, log=print,
-                    max_buffer_bytes=1 << 30):
+                    max_buffer_bytes=1 << 30, normals=False):
     """animate.py:104-118 / novel_view.py:117-127 for one rank of a job of `launch.world_size` ranks.
 
     The frames of `seq` are dealt round-robin to the ranks (parallel.shard_frames; frames are independent: no data-path
@@ -166,6 +190,8 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
     host memory asynchronously: the loop never waits for the GPU.  Frames whose wave-front loop needed more iterations than
     the graph holds are rendered again eagerly.  Every rank writes its own `<i>.png`; the GIF is written by rank 0 from the
     frames gathered there (RCCL gather of the packed images).
+    normals: the surface-normal pass is captured behind every frame and `normal_<i>.png` / `shaded_<i>.png` are written next to
+    `<i>.png` (packed on the device by one more launch, copied by the same copier stream; `<i>.png` is what it is without).
     Returns a dict: frames (of the sequence), local (rendered here), render_s (this rank's render loop, I/O and graph capture
     excluded), frames_per_sec (whole job: frames / max over ranks of render_s), incomplete (re-rendered frames)."""
     from .launch import Launch
@@ -179,15 +205,20 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
     # the packed frames stay on the device (the GIF gather travels over RCCL from there) and in pinned host memory (PNG encoding).
     # With a GIF every frame is kept until the end, as the reference does (animate.py:106-116); without one the sequence goes
     # through buffers of at most `max_buffer_bytes` (render a chunk, write its files, reuse the buffers)
-    per_frame = seq.H * seq.W * 4
+    per_frame = seq.H * seq.W * 4 * (3 if normals else 1)
     cap = n if gif else max(1, min(n, int(max_buffer_bytes) // per_frame))
     dev_frames = torch.empty((cap, seq.H, seq.W, 4), dtype=torch.uint8, device=dev)
     host = torch.empty((cap, seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=on_gpu)
+    if normals:      # [0]: normal images, [1]: shaded images
+        dev_extra = torch.empty((2, cap, seq.H, seq.W, 4), dtype=torch.uint8, device=dev)
+        host_extra = torch.empty((2, cap, seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=on_gpu)
+        rays_d_cam = seq.rays_d.reshape(-1, 3).contiguous()
     sync = torch.cuda.synchronize if on_gpu else (lambda: None)
     render_s, redo = 0.0, []
     if n:
         probes = [seq.batch(mine[(j * max(n // 8, 1)) % n]) for j in range(min(8, n))]   # wave-front loop length over the shard
-        renderer = (make_renderer or _make_renderer)(model, seq.batch(mine[0]), size, max(1, min(in_flight, n)), probes, jitter)
+        renderer = (make_renderer or _make_renderer)(model, seq.batch(mine[0]), size, max(1, min(in_flight, n)), probes, jitter,
+                                                     **({"normals": True} if normals else {}))
 
         # device -> host copies run on their own stream behind an event: a frame's stream goes straight on to its next frame
         # instead of standing still for the PCIe transfer (every frame of a chunk has its own slot: nothing is reused in flight)
@@ -195,15 +226,22 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
 
         def keep(slot):
             def consume(out, k):
-                pack_rgba8(out, dev_frames[slot])
+                pack_rgba8(out[:4], dev_frames[slot])
+                if normals:
+                    pack_normals8(out, rays_d_cam, dev_extra[0, slot], dev_extra[1, slot])
                 if copier is None:
                     host[slot].copy_(dev_frames[slot])
+                    if normals:
+                        host_extra[:, slot].copy_(dev_extra[:, slot])
                     return
                 ev = torch.cuda.Event()
                 ev.record()
                 copier.wait_event(ev)
                 with torch.cuda.stream(copier):
                     host[slot].copy_(dev_frames[slot], non_blocking=True)
+                    if normals:
+                        host_extra[0, slot].copy_(dev_extra[0, slot], non_blocking=True)
+                        host_extra[1, slot].copy_(dev_extra[1, slot], non_blocking=True)
             return consume
         with torch.inference_mode():
             for c0 in range(0, n, cap):
@@ -219,14 +257,18 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
                 renderer.finish()
                 bad = [c for c in renderer.incomplete_calls if c0 <= c < c1]     # (call number = position in `mine`)
                 for c in bad:
-                    keep(c - c0)(model.render_image_fast(seq.batch(mine[c]), size, jitter=jitter), 0)
+                    keep(c - c0)(model.render_image_fast(seq.batch(mine[c]), size, jitter=jitter, **({"normals": True} if normals else {})), 0)
                 sync()
                 redo += bad
                 if not gif:
                     write_frames(host[:c1 - c0].numpy(), out_dir, indices=mine[c0:c1])
+                    if normals:
+                        write_normal_frames(host_extra[0, :c1 - c0].numpy(), host_extra[1, :c1 - c0].numpy(), out_dir, mine[c0:c1])
     slowest = launch.max_over_ranks(render_s)
     if gif:
         write_frames(host.numpy(), out_dir, indices=mine)
+        if normals and n:
+            write_normal_frames(host_extra[0].numpy(), host_extra[1].numpy(), out_dir, mine)
         parts = launch.gather_to_main(dev_frames if launch.backend == "nccl" else host)
         if launch.is_main:
             w = launch.world_size
@@ -242,6 +284,9 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
 
 def add_launch_args(ap):
     ap.add_argument("--in-flight", type=int, default=3, help="frames in flight per GPU (captured HIP graphs replayed round-robin on their own streams)")
+    ap.add_argument("--normals", action="store_true",
+                    help="also write normal_<i>.png (surface normals of the posed density field, (n + 1) / 2 in the camera frame) and "
+                         "shaded_<i>.png (max(0, n . l), lit from the camera) next to <i>.png; SNARF deformer only")
     ap.add_argument("--jitter-seed", type=int, default=None,
                     help="use ONE occupancy-probe jitter for all frames (drawn from this seed) instead of a fresh draw per frame "
                          "(density_grid.py:98): the files no longer depend on how many ranks rendered the sequence")
@@ -308,7 +353,7 @@ def main(argv=None):
         seq = AnimateSequence(poses, trans, betas, device, args.downscale, size=args.size or None)
         jitter = None if args.jitter_seed is None else fixed_jitter(args.jitter_seed, device)
         res = render_sequence(model, seq, args.out, gif=None if args.no_gif else "animation.gif", launch=replica or launch,
-                              in_flight=args.in_flight, jitter=jitter, log=None if replica else print)
+                              in_flight=args.in_flight, jitter=jitter, log=None if replica else print, normals=args.normals)
         if replica is not None:
             # whole-job figure of the replicas: all frames of all subjects over the slowest rank's render loop
             slowest = launch.max_over_ranks(res["render_s"])

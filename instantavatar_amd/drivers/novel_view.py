@@ -117,7 +117,7 @@ def main(argv=None):
         seq = RotationSequence(args.frames, betas, device, args.downscale)
         jitter = None if args.jitter_seed is None else fixed_jitter(args.jitter_seed, device)
         res = render_sequence(model, seq, args.out, gif=None if args.no_gif else "rotation.gif", launch=launch,
-                              in_flight=args.in_flight, jitter=jitter)
+                              in_flight=args.in_flight, jitter=jitter, normals=args.normals)
         if launch.is_main:
             print("wrote %d frames (%dx%d) to %s" % (res["frames"], seq.W, seq.H, args.out))
     finally:

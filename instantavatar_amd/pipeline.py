@@ -25,17 +25,25 @@ class AvatarModel(torch.nn.Module):
         self.global_step = 0
         self.is_refine = False      # opt.optimize_SMPL.is_refine (confs/SNARF_NGP_refine.yaml): render with the refined SMPL tables
 
-    def forward(self, batch, eval_mode=True, noise=0):
-        """DNeRF.py:61-70"""
+    def _render(self, batch, eval_mode=True, noise=0):
+        """`forward`, also returning the rays in the marcher's frame"""
         rays = Rays(o=batch["rays_o"], d=batch["rays_d"], near=batch["near"], far=batch["far"])
         self.deformer.transform_rays_w2s(rays)
         return self.renderer(rays, lambda x, _: self.deformer(x, self.net_coarse, eval_mode), eval_mode=eval_mode,
-                             noise=noise, bg_color=batch.get("bg_color", None))
+                             noise=noise, bg_color=batch.get("bg_color", None)), rays
+
+    def forward(self, batch, eval_mode=True, noise=0):
+        """DNeRF.py:61-70"""
+        return self._render(batch, eval_mode, noise)[0]
 
     @torch.no_grad()
-    def render_image_fast(self, batch, img_size, jitter=None):
+    def render_image_fast(self, batch, img_size, jitter=None, normals=False):
         """DNeRF.py:72-97: (refinement: the frame's SMPL parameters come from the optimised tables, near / far follow the
-        refined translation -- :73-86), prepare deformer, rebuild the test occupancy grid, render."""
+        refined translation -- :73-86), prepare deformer, rebuild the test occupancy grid, render.
+        normals=True: a fifth element, the surface-normal map [1,H,W,3] of the frame in the camera frame
+        (`Raymarcher.render_normals`, launched behind the frame); the first four are what they are without it."""
+        if normals and not hasattr(self.deformer, "surface_normals"):
+            raise NotImplementedError("normals=True needs a deformer with `surface_normals` (the SNARF deformer)")
         if getattr(self, "SMPL_param", None) is not None and self.is_refine:
             idx = batch["idx_dev"] if torch.is_tensor(batch.get("idx_dev")) else batch["idx"].reshape(-1).long().to(batch["transl"].device)
             body_params = self.SMPL_param(idx.reshape(-1).long())
@@ -49,12 +57,15 @@ class AvatarModel(torch.nn.Module):
             batch["far"][:] = dist + 1
         self.deformer.prepare_deformer(batch)
         self.renderer.density_grid_test.initialize(self.deformer, self.net_coarse, jitter=jitter)
-        d = self.forward(batch, eval_mode=True)
+        d, rays = self._render(batch, eval_mode=True)
         rgb = d["rgb_coarse"].reshape(-1, *img_size, 3)
         depth = d["depth_coarse"].reshape(-1, *img_size)
         alpha = d["alpha_coarse"].reshape(-1, *img_size)
         counter = d["counter_coarse"].reshape(-1, *img_size)
-        return rgb, depth, alpha, counter
+        if not normals:
+            return rgb, depth, alpha, counter
+        nrm = self.renderer.render_normals(rays, self.deformer, self.net_coarse, d["depth_coarse"], d["alpha_coarse"])
+        return rgb, depth, alpha, counter, nrm.reshape(-1, *img_size, 3)
 
 
 class GraphedRenderer:
@@ -70,13 +81,15 @@ class GraphedRenderer:
     them; they must be re-rendered through `model.render_image_fast`).  `sync_check=True` checks
     before returning."""
 
-    def __init__(self, model, batch, img_size, warmup=3, margin=4, sync_check=False, probe_batches=(), jitter=None):
+    def __init__(self, model, batch, img_size, warmup=3, margin=4, sync_check=False, probe_batches=(), jitter=None, normals=False):
         """probe_batches: further batches (other poses of the sequence) rendered once eagerly to measure
         how many wave-front iterations the sequence needs; with a representative sample a small
         `margin` is enough (every idle iteration costs five empty launches per frame).
         jitter: a fixed occupancy-probe jitter ([5, 64^3, 3] in [0, 1), DensityGrid.initialize) read by every replay
-        instead of a fresh draw -- frames then depend on their pose only, whichever rank / replica / replay renders them."""
+        instead of a fresh draw -- frames then depend on their pose only, whichever rank / replica / replay renders them.
+        normals: the surface-normal pass is captured behind the frame; the outputs then have a fifth element (`render_image_fast`)."""
         self.model, self.img_size, self.sync_check, self.jitter = model, img_size, sync_check, jitter
+        self.normals = bool(normals)
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
         go, bp = self.static.get("global_orient"), self.static.get("body_pose")
         if torch.is_tensor(go) and torch.is_tensor(bp) and go.numel() == 3 and bp.numel() == 69 and go.dtype == bp.dtype == torch.float32:
@@ -90,7 +103,7 @@ class GraphedRenderer:
             model.render_image_fast(b, img_size, jitter=jitter)
             need = max(need, r.iters_executed())
         for _ in range(warmup):  # settles workspace sizes, fp16 shadows and the iteration count
-            model.render_image_fast(self.static, img_size, jitter=jitter)
+            model.render_image_fast(self.static, img_size, jitter=jitter, normals=self.normals)
             need = max(need, r.iters_executed())
         r._iters_hint = need + margin   # (no parity constraint: the alive lists ping-pong on the absolute iteration index)
         torch.cuda.synchronize()
@@ -100,7 +113,7 @@ class GraphedRenderer:
             # thread_local: other threads of the process (e.g. the RCCL watchdog of a multi-GPU job)
             # may touch the runtime while this thread captures
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.out = model.render_image_fast(self.static, img_size, jitter=jitter)
+                self.out = model.render_image_fast(self.static, img_size, jitter=jitter, normals=self.normals)
         finally:
             r._graph_capture = False
         # deferred alive check: a ring of pinned slots, polled without blocking -- the host may run up
@@ -179,7 +192,7 @@ class PipelinedRenderer:
     (2.2 ms latency), two 553, three 580."""
 
     def __init__(self, model, batch, img_size, n_in_flight=3, margin=1, probe_batches=(), jitter=None, priorities=None, schedule=None,
-                 max_queued=2):
+                 max_queued=2, normals=False):
         """schedule: "round_robin" (call i -> replica i mod n) or "least_loaded" (the replica with the fewest unfinished frames,
         the higher-priority one on a tie, at most `max_queued` frames queued per replica -- the host waits for the oldest one
         beyond that).  Default: IA_PIPELINE_SCHEDULE, else least loaded when the streams differ in priority (the high-priority
@@ -197,7 +210,8 @@ class PipelinedRenderer:
         for m, s in zip(self.replicas, self.streams):
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self.graphs.append(GraphedRenderer(m, batch, img_size, margin=margin, probe_batches=probe_batches, jitter=jitter))
+                self.graphs.append(GraphedRenderer(m, batch, img_size, margin=margin, probe_batches=probe_batches, jitter=jitter,
+                                                   normals=normals))
             torch.cuda.current_stream().wait_stream(s)
         self.events = [torch.cuda.Event() for _ in self.replicas]
         self.calls = 0

@@ -259,6 +259,15 @@ class Raymarcher(torch.nn.Module):
             "counter_coarse": counter.reshape(rays.near.shape),
         }
 
+    @torch.no_grad()
+    def render_normals(self, rays, deformer, net, depth, alpha):
+        """Surface-normal map of a frame rendered from `rays` (already in the marcher's frame: after
+        `deformer.transform_rays_w2s`), from its `depth_coarse` / `alpha_coarse`: rays.o.shape -> [..., 3] fp32 in the camera
+        frame, zero where alpha < 0.5 or the surface point has no valid canonical root, unit length elsewhere
+        (`SNARFDeformer.surface_normals`).  A second pass over at most one point per pixel."""
+        _lib.require_cuda(rays.o, rays.d, depth, alpha)
+        return deformer.surface_normals(rays.o, rays.d, depth, alpha, net).reshape(rays.o.shape)
+
     # ----------------------------------------------------------------- train
     def render_train_fused(self, rays, deformer, net, noise, bg_color):
         """render_train (raymarcher_acc.py:140-186) over COMPACT samples: march + jitter + compaction, deformation of the
