@@ -71,6 +71,9 @@ int ia_make_field_dev(const ia_field *f, FieldDev *out);
 int ia_launch_field(const float *x, int V, const int32_t *n_dev, const FieldDev &F, float *rgb, float *sigma,
                     hipStream_t s, uint16_t *acts);
 
+// the library's stream-ordered zero-fill (ia_smpl_nn.hip): a kernel, never a memset node.  bytes: multiple of 4; p: 16-byte aligned
+void ia_zero_fill(void *p, size_t bytes, hipStream_t s);
+
 // carves typed, 256-byte aligned pieces out of a caller-provided workspace
 struct WsCarver {
   char *base; size_t off, cap;

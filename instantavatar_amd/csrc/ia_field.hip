@@ -22,17 +22,7 @@
 //     the k-permutation is folded into the A (weight) fragments, which are
 //     built once per workgroup in LDS (22 fragments x 64 lanes x 16 B).
 #include "ia_common.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-#define N_FRAG 22
-#define F_SIG1 0   // [rb(2)][s(2)]
-#define F_SIG2 4   // [s(4)]
-#define F_COL1 8   // [rb(2)]
-#define F_COL2 10  // [rb(2)][s(4)]
-#define F_COL3 18  // [s(4)]
+#include "ia_field_dev.h"
 
 int ia_make_field_dev(const ia_field *f, FieldDev *o) {
   if (!f || !f->table || !f->sig_w1 || !f->sig_w2 || !f->col_w1 || !f->col_w2 || !f->col_w3) return -1;
@@ -74,51 +64,6 @@ int ia_make_field_dev(const ia_field *f, FieldDev *o) {
   return 0;
 }
 
-__device__ __forceinline__ _Float16 ld_h(const uint16_t *w, int idx) {
-  union { uint16_t u; _Float16 h; } c;
-  c.u = w[idx];
-  return c.h;
-}
-
-// Weight value of A-fragment f at lane (i = out row in its 32-block, h) and
-// position p (0..7).  k-permutations explained in the file header.
-template <int L>
-__device__ _Float16 frag_value(const FieldDev &F, int f, int i, int h, int p) {
-  const int kk = (p & 3) + 8 * (p >> 2) + 4 * h;  // C/D row order inside a 16-row slab
-  if (f < F_SIG2) {
-    const int rb = f >> 1, s = f & 1;
-    if (s >= L / 8) return (_Float16)0.f;
-    return ld_h(F.sig_w1, (rb * 32 + i) * (2 * L) + h * L + 8 * s + p);
-  }
-  if (f < F_COL1) {
-    const int s = f - F_SIG2;
-    return i < 16 ? ld_h(F.sig_w2, i * 64 + 16 * s + kk) : (_Float16)0.f;
-  }
-  if (f < F_COL2) {
-    // colour input c[m] = out[m+1] (m < 15), c[15] = 1 (tcnn identity padding);
-    // our B slot kk holds out[kk] for kk >= 1 and the constant 1 at kk == 0.
-    const int rb = f - F_COL1;
-    return ld_h(F.col_w1, (rb * 32 + i) * 16 + (kk == 0 ? 15 : kk - 1));
-  }
-  if (f < F_COL3) {
-    const int rb = (f - F_COL2) >> 2, s = (f - F_COL2) & 3;
-    return ld_h(F.col_w2, (rb * 32 + i) * 64 + 16 * s + kk);
-  }
-  const int s = f - F_COL3;
-  return i < 16 ? ld_h(F.col_w3, i * 64 + 16 * s + kk) : (_Float16)0.f;
-}
-
-__device__ __forceinline__ void normalise(const FieldDev &F, const float *__restrict__ x, size_t i,
-                                          float xn[3]) {
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    float v = (x[i * 3 + d] - F.center[d]) / F.scale[d] + 0.5f;  // ngp.py:75
-    v = v < 0.f ? 0.f : v;                                       // ngp.py:77 clamp
-    v = v > 1.f ? 1.f : v;
-    xn[d] = v;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // One level of the hash grid for one sample -> packed (f0,f1) half2.
 //
@@ -142,13 +87,7 @@ __device__ __forceinline__ void level_loads(const uint32_t *__restrict__ tab, fl
                                             uint32_t size, const float xn[3], float w[3], uint32_t lo[4],
                                             uint32_t hi[4], uint32_t ext[4], uint32_t &meta) {
   uint32_t g[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) {  // tcnn pos_fract
-    const float pos = __builtin_fmaf(xn[d], scale, 0.5f);  // nvcc contracts tcnn's `input * scale + 0.5f`
-    const float fl = floorf(pos);
-    g[d] = (uint32_t)(int)fl;
-    w[d] = pos - fl;
-  }
+  pos_fract(xn, scale, g, w);
   meta = 0;
   if (KIND == 2) {
     // hashed level (coherent prime hash, 2^k entries): eight independent 4-byte gathers.
@@ -322,13 +261,7 @@ __device__ __forceinline__ void hashed_quad_loads(const uint32_t *__restrict__ t
                                                   float w[3], uint32_t qx[4], uint32_t qy[4], uint32_t qz[4], uint32_t qw[4],
                                                   uint32_t ext[4], uint32_t &meta) {
   uint32_t g[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    const float pos = __builtin_fmaf(xn[d], scale, 0.5f);
-    const float fl = floorf(pos);
-    g[d] = (uint32_t)(int)fl;
-    w[d] = pos - fl;
-  }
+  pos_fract(xn, scale, g, w);
   const bool far = (g[0] & 3u) == 3u;   // x + 1 carries out of the two low bits: its entry lies in another group
   meta = far ? (1u << 16) : 0u;
 #pragma unroll
@@ -455,20 +388,6 @@ static int ia_launch_encode_xcd(const float *x, int V, const int32_t *n_dev, con
   IA_LAUNCH_CHECK("k_encode_xcd");
   return IA_OK;
 }
-
-template <bool RELU>
-__device__ __forceinline__ half8 pack_slab(const floatx16 &acc, int sub) {
-  half8 o;
-#pragma unroll
-  for (int p = 0; p < 8; p++) {
-    float v = acc[8 * sub + p];
-    if (RELU) v = v < 0.f ? 0.f : v;
-    o[p] = (_Float16)v;
-  }
-  return o;
-}
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 
 // activation record written in training mode (fp16, IA_ACT_STRIDE halves per sample):
 //   [0,2L) hash features | h1 (64) | sigma-net output (16) | c1 (64) | c2 (64)
@@ -798,8 +717,6 @@ extern "C" int ia_field_fwd_train(const float *x, int V, const int32_t *n_dev, c
 #define R_AH1 368
 #define R_AF 432
 #define R_TOTAL 464
-
-__device__ __forceinline__ int cd_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // 4 consecutive rows (8g + 4h + q) of a saved activation -> 4 halves
 __device__ __forceinline__ void load4(const uint16_t *__restrict__ rec, int off, bool valid, _Float16 *o) {
@@ -1203,7 +1120,7 @@ __global__ __launch_bounds__(256) void k_hashgrid_bwd(const float *__restrict__ 
       float w[3];
       uint32_t g[3];
 #pragma unroll
-      for (int d = 0; d < 3; d++) {
+      for (int d = 0; d < 3; d++) {   // pos_fract (ia_field_dev.h), spelled out: the call changes this unit's device code
         const float pos = __builtin_fmaf(xn[d], scale, 0.5f);
         const float fl = floorf(pos);
         g[d] = (uint32_t)(int)fl;
@@ -1234,7 +1151,7 @@ __global__ __launch_bounds__(256) void k_hashgrid_bwd(const float *__restrict__ 
 #pragma unroll
       for (int idx = 0; idx < 8; idx++) {
         const uint32_t cx = g[0] + (idx & 1), cy = g[1] + ((idx >> 1) & 1), cz = g[2] + ((idx >> 2) & 1);
-        uint32_t index;
+        uint32_t index;   // corner_index (ia_field_dev.h), spelled out for the same reason
         if (hashed) {
           index = (cx ^ (cy * 2654435761u) ^ (cz * 805459861u)) & (size - 1);
         } else {

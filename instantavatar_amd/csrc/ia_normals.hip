@@ -7,19 +7,12 @@
 //   8-bit images of (n + 1) / 2 and of max(0, n . l)                           (ia_pack_normals8)
 // The definition is stated in DESIGN.md section 4 and in include/instantavatar_hip_normals.h.  Nothing here synchronises, allocates or reads on the host.
 //
-// The device functions of the field's encoder and of the sigma network live in ia_field.hip; they are RESTATED here (same
-// expressions, same order) instead of being moved into a header, so that the device code of the existing translation units
-// stays byte-identical (bench.py keys its counter evidence on their hashes).  ia_field_sigma_grad's sigma is tested bit for
-// bit against ia_field_fwd's (tests/test_gpu_normals.py), which is what holds the two copies together.
+// The vector types, the A fragments of the sigma network (frag_value, pack_slab, MFMA), the normalisation of a sample and the
+// cell / corner arithmetic of a hash-grid level come from ia_field_dev.h, which ia_field.hip uses too.
 #include "ia_common.h"
+#include "ia_field_dev.h"
 #include "ia_search_dev.h"
 #include "../../include/instantavatar_hip_normals.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // surface points: deterministic compaction in ray order
@@ -115,9 +108,9 @@ extern "C" int ia_surface_points(const float *rays_o, const float *rays_d, const
 // ---------------------------------------------------------------------------------------------------------------------
 // sigma and d sigma / d x of the sigma network in one kernel
 // ---------------------------------------------------------------------------------------------------------------------
-// Forward: ia_field.hip's chain restated -- one lane encodes one sample (per level: eight corner products in fp32, rounded to
-// half and accumulated in half, in corner order), lanes j and j + 32 exchange half of their levels, the two 32-sample column
-// blocks go through the SAME MFMA sequence with the same A fragments (sigma-net layer 1 [64 x 2L], ReLU + rounding to half,
+// Forward: ia_field.hip's chain on the shared device functions -- one lane encodes one sample (per level: eight corner
+// products in fp32, rounded to half and accumulated in half, in corner order), lanes j and j + 32 exchange half of their
+// levels, the two 32-sample column blocks go through the SAME MFMA sequence with the same A fragments (sigma-net layer 1 [64 x 2L], ReLU + rounding to half,
 // layer 2 [16 x 64]); sigma = half(out[0]).  Same operands in the same instructions: the same bits.
 // Backward (one output channel: a GEMV chain per sample, no MFMA): the C/D layout leaves hidden unit 32 rb + (r & 3) +
 // 8 (r >> 2) + 4 h of sample j in register r of accumulator rb of lane (j, h).  Each of the two lanes forms
@@ -131,64 +124,17 @@ extern "C" int ia_surface_points(const float *rays_o, const float *rays_d, const
 #define IA_SG_THREADS 256
 #define IA_SG_WAVES (IA_SG_THREADS / 64)
 
-__device__ __forceinline__ _Float16 sg_ld_h(const uint16_t *w, int idx) {
-  union { uint16_t u; _Float16 h; } c;
-  c.u = w[idx];
-  return c.h;
-}
-
-// A fragments 0..3 (layer 1: [rb][s]) and 4..7 (layer 2: [s]) of ia_field.hip's frag_value
-template <int L>
-__device__ _Float16 sg_frag_value(const FieldDev &F, int f, int i, int h, int p) {
-  const int kk = (p & 3) + 8 * (p >> 2) + 4 * h;
-  if (f < 4) {
-    const int rb = f >> 1, s = f & 1;
-    if (s >= L / 8) return (_Float16)0.f;
-    return sg_ld_h(F.sig_w1, (rb * 32 + i) * (2 * L) + h * L + 8 * s + p);
-  }
-  const int s = f - 4;
-  return i < 16 ? sg_ld_h(F.sig_w2, i * 64 + 16 * s + kk) : (_Float16)0.f;
-}
-
-template <bool RELU>
-__device__ __forceinline__ half8 sg_pack_slab(const floatx16 &acc, int sub) {
-  half8 o;
-#pragma unroll
-  for (int p = 0; p < 8; p++) {
-    float v = acc[8 * sub + p];
-    if (RELU) v = v < 0.f ? 0.f : v;
-    o[p] = (_Float16)v;
-  }
-  return o;
-}
-
-// corner indices and fractional position of one level for one sample (ia_field.hip: level_loads; k_hashgrid_bwd's index form)
+// fractional position and the eight corner entries of one level for one sample, in corner order
 __device__ __forceinline__ void sg_corners(const uint32_t *__restrict__ tab, float scale, uint32_t res, uint32_t size, bool hashed,
                                            const float xn[3], float w[3], uint32_t raw[8]) {
   uint32_t g[3];
+  pos_fract(xn, scale, g, w);
 #pragma unroll
-  for (int d = 0; d < 3; d++) {
-    const float pos = __builtin_fmaf(xn[d], scale, 0.5f);
-    const float fl = floorf(pos);
-    g[d] = (uint32_t)(int)fl;
-    w[d] = pos - fl;
-  }
-#pragma unroll
-  for (int idx = 0; idx < 8; idx++) {
-    const uint32_t cx = g[0] + (idx & 1), cy = g[1] + ((idx >> 1) & 1), cz = g[2] + ((idx >> 2) & 1);
-    uint32_t index;
-    if (hashed) {
-      index = (cx ^ (cy * 2654435761u) ^ (cz * 805459861u)) & (size - 1);
-    } else {
-      index = cx + cy * res + cz * res * res;
-      if (index >= size) index -= size;
-      index = min(index, size - 1);   // memory safety for non-finite inputs
-    }
-    raw[idx] = tab[index];
-  }
+  for (int idx = 0; idx < 8; idx++)
+    raw[idx] = tab[corner_index(hashed, g[0] + (idx & 1), g[1] + ((idx >> 1) & 1), g[2] + ((idx >> 2) & 1), res, size)];
 }
 
-// packed (f0, f1) half2 of one level as ia_field.hip's level_reduce forms it
+// packed (f0, f1) half2 of one level: the accumulation of ia_field.hip's level_reduce<2>, which defines it, on a flat raw[8]
 __device__ __forceinline__ uint32_t sg_level_feat(const float w[3], const uint32_t raw[8]) {
   _Float16 r0 = (_Float16)0.f, r1 = (_Float16)0.f;
 #pragma unroll
@@ -245,11 +191,11 @@ __global__ __launch_bounds__(IA_SG_THREADS) void k_sigma_grad(const float *__res
   } else {
     for (int e = threadIdx.x; e < 8 * 64 * 8; e += IA_SG_THREADS) {
       const int f = e >> 9, l = (e >> 3) & 63, p = e & 7;
-      reinterpret_cast<_Float16 *>(&s_frag[f][l])[p] = sg_frag_value<L>(F, f, l & 31, l >> 5, p);
+      reinterpret_cast<_Float16 *>(&s_frag[f][l])[p] = frag_value<L>(F, f, l & 31, l >> 5, p);
     }
   }
-  for (int e = threadIdx.x; e < 64 * 2 * L; e += IA_SG_THREADS) s_w1[e] = sg_ld_h(F.sig_w1, e);
-  if (threadIdx.x < 64) s_w2[threadIdx.x] = (float)sg_ld_h(F.sig_w2, threadIdx.x);
+  for (int e = threadIdx.x; e < 64 * 2 * L; e += IA_SG_THREADS) s_w1[e] = ld_h(F.sig_w1, e);
+  if (threadIdx.x < 64) s_w2[threadIdx.x] = (float)ld_h(F.sig_w2, threadIdx.x);
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int h = lane >> 5, j = lane & 31;
@@ -258,14 +204,10 @@ __global__ __launch_bounds__(IA_SG_THREADS) void k_sigma_grad(const float *__res
     float xn[3] = {0.f, 0.f, 0.f};
     bool inside[3] = {false, false, false};
     if (i < V) {
+      normalise(F, x, (size_t)i, xn);
+      // d xn / d x = 1 / scale inside the unit cube, 0 where the clamp is active (xn is exactly 0 or 1 there; NaN: 0 as well)
 #pragma unroll
-      for (int d = 0; d < 3; d++) {
-        float v = (x[(size_t)i * 3 + d] - F.center[d]) / F.scale[d] + 0.5f;   // ia_field.hip: normalise
-        inside[d] = v > 0.f && v < 1.f;   // d xn / d x = 1 / scale inside the unit cube, 0 where the clamp is active
-        v = v < 0.f ? 0.f : v;
-        v = v > 1.f ? 1.f : v;
-        xn[d] = v;
-      }
+      for (int d = 0; d < 3; d++) inside[d] = xn[d] > 0.f && xn[d] < 1.f;
     }
     uint32_t feat[L];
 #pragma unroll
@@ -307,7 +249,7 @@ __global__ __launch_bounds__(IA_SG_THREADS) void k_sigma_grad(const float *__res
       a2 = (floatx16){0.f};
 #pragma unroll
       for (int s = 0; s < 4; s++)
-        a2 = MFMA(s_frag[4 + s][lane], (s & 1) ? sg_pack_slab<true>(a1[s >> 1], 1) : sg_pack_slab<true>(a1[s >> 1], 0), a2);
+        a2 = MFMA(s_frag[4 + s][lane], (s & 1) ? pack_slab<true>(a1[s >> 1], 1) : pack_slab<true>(a1[s >> 1], 0), a2);
       const int o = tile * 64 + cb * 32 + j;
       if (h == 0 && o < V) sigma[o] = (float)(_Float16)a2[0];   // row 0 lives in lanes h == 0
       // ---- backward through this lane's 32 hidden units ----
@@ -325,7 +267,7 @@ __global__ __launch_bounds__(IA_SG_THREADS) void k_sigma_grad(const float *__res
       // (a rolled loop over the lane's 32 units, the mask in a register: unrolled, the weight rows of all 32 are hoisted and spill)
 #pragma unroll 2
       for (int t = 0; t < 32; t++) {
-        const int r = t & 15, k = 32 * (t >> 4) + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int k = 32 * (t >> 4) + cd_row(t & 15, h);
         const float dh = ((on >> t) & 1u) ? s_w2[k] : 0.f;
         const half8 *row = reinterpret_cast<const half8 *>(s_w1 + k * 2 * L);
 #pragma unroll
@@ -427,10 +369,6 @@ extern "C" int ia_candidate_select(const float *cand_sigma, const float *cand_xc
 // ---------------------------------------------------------------------------------------------------------------------
 // normals from gradients
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_zero_f32(float *__restrict__ p, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0.f;
-}
-
 // One lane = one point.  M = linear part of the trilinearly interpolated transform grid at the root (the search's fetch:
 // 8 corner records of 48 B, corners outside the grid with weight 0), v = cof(M) g (= det(M) M^{-T} g, rows of cof(M) are
 // the cross products of the rows of M), n = -sign(det) v, rotated by the transpose of w2s' rotation and normalised.
@@ -492,10 +430,9 @@ extern "C" int ia_normals_from_gradient(const float *root, const float *grad, co
   IA_CHECK_ARG(n >= 0 && R >= 0, "ia_normals_from_gradient: negative size");
   if (R == 0) return IA_OK;
   IA_CHECK_ARG(normals, "ia_normals_from_gradient: null pointer");
-  // the map is zero-filled by a kernel, not by a memset node (NOTES.md: replayed graphs)
-  int zb = ia_div_up((long)R * 3, 256);
-  if (zb > 2048) zb = 2048;
-  hipLaunchKernelGGL(k_zero_f32, dim3(zb), dim3(256), 0, (hipStream_t)stream, normals, (size_t)R * 3);
+  // the map is zero-filled by a kernel, not by a memset node (NOTES.md: replayed graphs); 12 R bytes, 16-byte stores
+  IA_CHECK_ARG((reinterpret_cast<uintptr_t>(normals) & 15) == 0, "ia_normals_from_gradient: the map must be 16-byte aligned");
+  ia_zero_fill(normals, (size_t)R * 12, (hipStream_t)stream);
   if (n > 0) {
     IA_CHECK_ARG(root && grad && ray_idx && voxel_J && grid && w2s, "ia_normals_from_gradient: null pointer");
     IA_CHECK_ARG(grid->D > 0 && grid->H > 0 && grid->W > 0 && (long)grid->D * grid->H * grid->W * 48 < (1l << 32),

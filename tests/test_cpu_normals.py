@@ -22,6 +22,8 @@ def test_new_prototypes_are_declared_and_exported():
     from instantavatar_amd import build
     import os
     assert "ia_normals.hip" in build.SOURCES
+    for unit in ("ia_field.hip", "ia_normals.hip"):      # an edit of the shared device header invalidates both source hashes
+        assert "ia_field_dev.h" in [os.path.basename(h) for h in build.includes_of(os.path.join(build.CSRC, unit))], unit
     assert os.path.normpath(_lib.NORMALS_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
 
 

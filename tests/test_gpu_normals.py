@@ -163,8 +163,8 @@ def test_normals_from_gradient():
     grad[20:60] = 0.0                                                # zero gradients
     grad[60:70] *= np.float32(1e-30)                                 # tiny and huge, finite
     grad[70:80] *= np.float32(1e30)
-    ray = rng.permutation(3000)[:n].astype(np.int32)                 # scattered into a map of 3000 rays
-    R = 3000
+    ray = rng.permutation(3000)[:n].astype(np.int32)                 # scattered into a map of 3001 rays: 9003 words, so the
+    R = 3001                                                         # zero-fill's 16-byte body AND its tail of three words run
     w2s = np.eye(4, dtype=np.float32)
     w2s[:3, :3] = _rotation(rng)
     w2s[:3, 3] = [0.3, -0.2, 4.0]
@@ -173,7 +173,7 @@ def test_normals_from_gradient():
     gd = L.SnarfGrid()
     gd.D, gd.H, gd.W = D, H, W
     gd.offset[:], gd.scale[:] = grid["offset"].tolist(), grid["scale"].tolist()
-    out = torch.full((R, 3), 9.0, device=DEV)
+    out = torch.full((R, 3), float("nan"), device=DEV)               # whatever the call does not write must have been zero-filled
     n_dev = torch.tensor([n - 100], dtype=torch.int32, device=DEV)   # the last 100 points are not live
     L.call("ia_normals_from_gradient", _dev(root), _dev(grad), _dev(ray), n, n_dev, _dev(vJ.reshape(-1)), gd, _dev(w2s), R, out)
     torch.cuda.synchronize()
@@ -188,6 +188,19 @@ def test_normals_from_gradient():
     assert (got[zero] == 0).all(), "a pixel without a normal is not exactly zero"
     assert np.abs(got[~zero] - want[~zero]).max() <= 1e-5, float(np.abs(got[~zero] - want[~zero]).max())
     assert np.abs(np.linalg.norm(got[~zero], axis=1) - 1).max() <= 1e-6
+    # a small map, far more pixels than points: 301 rays (903 words: less than one workgroup of 16-byte stores, and a tail), 200 points
+    R2, n2 = 301, 200
+    ray2 = rng.permutation(R2)[:n2].astype(np.int32)
+    out2 = torch.full((R2, 3), float("nan"), device=DEV)
+    L.call("ia_normals_from_gradient", _dev(root[:n2]), _dev(grad[:n2]), _dev(ray2), n2, None, _dev(vJ.reshape(-1)), gd, _dev(w2s), R2, out2)
+    torch.cuda.synchronize()
+    got2 = _np(out2).astype(np.float64)
+    want2 = np.zeros((R2, 3))
+    want2[ray2] = ref[:n2]
+    zero2 = (want2 == 0).all(1)
+    assert zero2.sum() >= R2 - n2 + 60 and (~zero2).sum() > 10
+    assert np.array_equal(got2[zero2], np.zeros((int(zero2.sum()), 3))), "a pixel without a normal is not exactly zero (small map)"
+    assert np.abs(got2[~zero2] - want2[~zero2]).max() <= 1e-5
 
 
 # ---- the 8-bit images -------------------------------------------------------------------------------------------------
