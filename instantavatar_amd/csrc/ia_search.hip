@@ -9,8 +9,10 @@
 //
 // What bounds it (round 4; profiles/r04_search_phase_cycles.txt, r04_ab_search_occupancy_cellcache.txt): the
 // solver loop is a dependent chain -- fetch plan, three load round trips, row delivery through LDS, the Broyden update -- whose
-// latency the four waves per SIMD that 106 VGPRs allow hide only in part (3 / 2 workgroups per CU: 205 / 253 us against 191).  A
-// wave-step moves 24.6 KB through the CU's vector L1 and issues 380-480 VALU instructions; at one wave-step per ~575 CU-cycles
+// latency the four waves per SIMD that 110 VGPRs allow hide only in part (3 / 2 workgroups per CU: 205 / 253 us against 191).  A
+// wave-step moves 24.6 KB through the CU's vector L1 and issued 380-480 VALU instructions up to round 6 (round 7 took 16 % of
+// the executed VALU instructions out: weights through LDS, the Broyden update in packed pairs, the bench-only counters in an
+// instantiation of their own -- profiles/r07_ab_search_valu.txt); at one wave-step per ~575 CU-cycles
 // both pipes are two-thirds busy and neither is the limit (a register cell cache that removed 35 % of the loads gained 1.4 %
 // and lost 31 % through its registers).  A persistent-wave rewrite (no workgroup barrier, global work supply, lanes packed 15 %
 // tighter, bit-identical) lost by 12 %: more waves inside the loop only lengthen every round trip.  All archived with their
@@ -44,7 +46,9 @@
 #define IA_SEARCH_THREADS 256  // 256 x 128 212.1, 128 x 64 215.3, 64 x 32 223.0, 256 x 32 228.6, 512 x 64 229.2
 #define IA_SEARCH_ATTR
 
-template <int MODE>
+// PROF: the bench-only accounting (solves, fetches, fetches that touched memory) is a template parameter -- the product loop
+// carries neither the counters nor their updates; the counting instantiation runs only under ia_profile_enable.
+template <int MODE, bool PROF>
 __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
     const float *__restrict__ xd, int P, const int32_t *__restrict__ n_pts_dev,
     const float *__restrict__ vJ, const float *__restrict__ tfs, BoneIds bones, int n_init, SnarfGridDev g,
@@ -74,6 +78,8 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
   __shared__ float s_T[IA_N_INIT_MAX][12];  // rows 0..2 of the init bones' transforms (same indexing as the 4x4)
   __shared__ float4 s_del_store[IA_SEARCH_THREADS * 3];
   float4 *const s_del = s_del_store;
+  __shared__ float4 s_wt[IA_WT_HALF * 2];  // the 8 trilinear weights of every lane's fetch, for the lanes that serve it
+  static_assert(IA_WT_HALF == IA_SEARCH_THREADS, "s_wt: one plane per half of the weights, a slot per thread");
   if (n_pts_dev) P = min(P, *n_pts_dev);
   const int tid = threadIdx.x, lane = tid & 63;
   // (an XCD-aware remap -- XCD x takes the x-th contiguous eighth of the point list -- was measured:
@@ -131,10 +137,11 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
   int item = 0;
   uint32_t counts = 0, it_solves = 0;
   float t0 = 0, t1 = 0, t2 = 0;
-  float xl0 = 0, xl1 = 0, xl2 = 0, gx0 = 0, gx1 = 0, gx2 = 0, u0 = 0, u1 = 0, u2 = 0;
-  float Ji[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) Ji[k] = 0.f;
+  // (x, g, u and J_inv as register pairs + a scalar: see JinvPairs in ia_search_dev.h)
+  ia_f2 xl01 = (ia_f2){0.f, 0.f}, gx01 = xl01, u01 = xl01;
+  float xl2 = 0, gx2 = 0, u2 = 0;
+  JinvPairs Ji;
+  Ji.P = Ji.Q = Ji.R = Ji.S = xl01; Ji.J22 = 0.f;
   bool queue_empty = false;
   while (true) {
     if (!queue_empty) {
@@ -152,22 +159,23 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
           const float *T = s_T[init];
           // :287-293  x0 = R^T (xd - t)
           const float ixd = t0 - T[3], iyd = t1 - T[7], izd = t2 - T[11];
-          xl0 = IA_DOT3(ixd, T[0], iyd, T[4], izd, T[8]);
-          xl1 = IA_DOT3(ixd, T[1], iyd, T[5], izd, T[9]);
+          xl01.x = IA_DOT3(ixd, T[0], iyd, T[4], izd, T[8]);
+          xl01.y = IA_DOT3(ixd, T[1], iyd, T[5], izd, T[9]);
           xl2 = IA_DOT3(ixd, T[2], iyd, T[6], izd, T[10]);
-          active = true; first = true; it_solves = (it_solves & ~0xFFu) + 0x100u;
+          active = true; first = true; it_solves = (it_solves & ~0xFFu) + (PROF ? 0x100u : 0u);
         }
       }
     }
     if (!__any(active)) break;
+    const float xl0 = xl01.x, xl1 = xl01.y;
     const float ix = g.scl[0] * (xl0 + g.off[0]);
     const float iy = g.scl[1] * (xl1 + g.off[1]);
     const float iz = g.scl[2] * (xl2 + g.off[2]);
     float Jl[12];
     bool ld = false;
-    fetch_J_quad(vJ, g, ix, iy, iz, active, Jl, ld, s_del);   // all lanes: the quad serves its four fetches together
+    fetch_J_quad(vJ, g, ix, iy, iz, active, Jl, ld, s_del, s_wt);   // all lanes: the quad serves its four fetches together
     if (active) {
-      counts += ld ? 0x10001u : 1u;
+      if (PROF) counts += ld ? 0x10001u : 1u;
       bool done = false, ok = false;
       // residual g(x) = J x + d - x_d at the current point (:325-332 initial, :356-367 updated)
       const float n0 = IA_DOT3(Jl[0], xl0, Jl[1], xl1, Jl[2], xl2) + Jl[3] - t0;
@@ -175,9 +183,10 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
       const float n2 = IA_DOT3(Jl[8], xl0, Jl[9], xl1, Jl[10], xl2) + Jl[11] - t2;
       if (first) {
         // :302-311 J_inv0 = (J_3x3)^T
-        Ji[0] = Jl[0]; Ji[1] = Jl[4]; Ji[2] = Jl[8]; Ji[3] = Jl[1]; Ji[4] = Jl[5]; Ji[5] = Jl[9];
-        Ji[6] = Jl[2]; Ji[7] = Jl[6]; Ji[8] = Jl[10];
-        gx0 = n0; gx1 = n1; gx2 = n2;
+        Ji.P = (ia_f2){Jl[0], Jl[1]}; Ji.Q = (ia_f2){Jl[4], Jl[5]}; Ji.R = (ia_f2){Jl[8], Jl[9]};
+        Ji.S = (ia_f2){Jl[2], Jl[6]}; Ji.J22 = Jl[10];
+        gx01 = (ia_f2){n0, n1}; gx2 = n2;
+        jinv_neg_apply(Ji, gx01, gx2, u01, u2);
         first = false;
       } else {
         // :368-398 convergence / divergence tests
@@ -188,44 +197,46 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
         } else if (norm > dvg2) {
           done = true;
         } else {
-          jinv_update(Ji, u0, u1, u2, n0 - gx0, n1 - gx1, n2 - gx2);  // :400-411
-          gx0 = n0; gx1 = n1; gx2 = n2;
+          jinv_update(Ji, u01, u2, (ia_f2){n0, n1} - gx01, n2 - gx2);  // :400-411
+          gx01 = (ia_f2){n0, n1}; gx2 = n2;
+          jinv_neg_apply(Ji, gx01, gx2, u01, u2);
           if ((++it_solves & 0xFFu) == 10u) done = true;  // Q1: not converged after 10 iterations -> invalid
         }
       }
       if (done) {
         const int init = item >> 7, pt = item & (NP - 1);
-        s_x[init][pt][0] = ok ? xl0 : 0.f; s_x[init][pt][1] = ok ? xl1 : 0.f; s_x[init][pt][2] = ok ? xl2 : 0.f;
-        s_valid[init][pt] = ok;
+        const int slot = init * NP + pt;   // one index for s_x and s_valid: a shift-or and one 24-bit multiply by 12
+        float *const sx = &s_x[0][0][0] + slot * 3;
+        sx[0] = ok ? xl0 : 0.f; sx[1] = ok ? xl1 : 0.f; sx[2] = ok ? xl2 : 0.f;
+        (&s_valid[0][0])[slot] = ok;
         if (ok) it_solves |= 0x80000000u;   // this lane found a root (bit 31: `solves` stays below 2^16)
+        float Jk[9];
+        if (MODE != 1) Ji.store(Jk);
         if (MODE == 0 && J_inv) {
           // Q4: the stored J_inv is the matrix BEFORE the last rank-1 update (:383-391)
           const size_t o = ((size_t)(p0 + pt) * n_init + init) * 9;
 #pragma unroll
-          for (int k = 0; k < 9; k++) J_inv[o + k] = ok ? Ji[k] : 0.f;
+          for (int k = 0; k < 9; k++) J_inv[o + k] = ok ? Jk[k] : 0.f;
         }
         if (MODE == 2 && ok) {
 #pragma unroll
-          for (int k = 0; k < 9; k++) jinv_dense[((size_t)(p0 + pt) * n_init + init) * 9 + k] = Ji[k];  // Q4 as above
+          for (int k = 0; k < 9; k++) jinv_dense[((size_t)(p0 + pt) * n_init + init) * 9 + k] = Jk[k];  // Q4 as above
         }
         active = false;
       } else {
         // :340-351 update = -J_inv g ; x += update (start of the next iteration)
-        u0 = IA_DOT3(-Ji[0], gx0, -Ji[1], gx1, -Ji[2], gx2);
-        u1 = IA_DOT3(-Ji[3], gx0, -Ji[4], gx1, -Ji[5], gx2);
-        u2 = IA_DOT3(-Ji[6], gx0, -Ji[7], gx1, -Ji[8], gx2);
-        xl0 += u0; xl1 += u1; xl2 += u2;
+        xl01 += u01; xl2 += u2;
       }
     }
   }
-  if (prof) {  // bench-only accounting: solves and trilinear fetches
+  if (PROF) {  // bench-only accounting: solves and trilinear fetches
     int f = (int)(counts & 0xFFFFu), n = (int)((it_solves >> 8) & 0xFFFFu), l = (int)(counts >> 16);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { f += __shfl_xor(f, o, 64); n += __shfl_xor(n, o, 64); l += __shfl_xor(l, o, 64); }
     if (lane == 0) { atomicAdd(&s_prof[0], n); atomicAdd(&s_prof[1], f); atomicAdd(&s_prof[2], l); }
   }
   const int any_root = __syncthreads_or((int)(it_solves >> 31));
-  if (prof && tid == 0) {  // one pair of global atomics per workgroup, on a per-shard line
+  if (PROF && tid == 0) {  // one pair of global atomics per workgroup, on a per-shard line
     unsigned long long *ps = prof + (size_t)(blockIdx.x & (IA_PROF_SHARDS - 1)) * 8;
     atomicAdd(ps, (unsigned long long)s_prof[0]);
     atomicAdd(ps + 1, (unsigned long long)s_prof[1]);
@@ -325,7 +336,7 @@ extern "C" int ia_snarf_search(const float *xd, int P, const float *voxel_J, con
   IA_CHECK_ARG(xd && voxel_J && tfs && grid && xc && valid, "ia_snarf_search: null pointer");
   BoneIds b;
   IA_CHECK_ARG(ia_make_bones(bone_ids, n_init, &b) == 0, "ia_snarf_search: bad bone ids / n_init=%d", n_init);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search<0>), dim3(ia_div_up(P, IA_SEARCH_NP)), dim3(IA_SEARCH_THREADS), 0,
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search<0, false>), dim3(ia_div_up(P, IA_SEARCH_NP)), dim3(IA_SEARCH_THREADS), 0,
                      (hipStream_t)stream, xd, P, (const int32_t *)nullptr, voxel_J, tfs, b, n_init,
                      ia_make_grid_dev(grid), cvg_thresh * cvg_thresh, dvg_thresh * dvg_thresh, xc, valid,
                      valid_raw, J_inv, (float *)nullptr, 0, (int32_t *)nullptr, (uint8_t *)nullptr,
@@ -349,16 +360,18 @@ static int ia_search_compact_impl(const char *who, const float *xd, int P, const
   const dim3 grd(ia_div_up(P, IA_SEARCH_NP)), blk(IA_SEARCH_THREADS);
   const SnarfGridDev g = ia_make_grid_dev(grid);
   ia_prof_begin(IA_PROF_SEARCH, s);
-  if (with_jinv)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search<2>), grd, blk, 0, s, xd, P, n_pts_dev, voxel_J, tfs, b, n_init, g,
-                       cvg_thresh * cvg_thresh, dvg_thresh * dvg_thresh, (float *)nullptr, (uint8_t *)nullptr,
-                       (uint8_t *)nullptr, (float *)nullptr, cand_xc, cand_cap, pt_off, pt_cnt, n_cand,
-                       ia_prof_units(IA_PROF_SEARCH), cand_Jinv, jinv_dense);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search<1>), grd, blk, 0, s, xd, P, n_pts_dev, voxel_J, tfs, b, n_init, g,
-                       cvg_thresh * cvg_thresh, dvg_thresh * dvg_thresh, (float *)nullptr, (uint8_t *)nullptr,
-                       (uint8_t *)nullptr, (float *)nullptr, cand_xc, cand_cap, pt_off, pt_cnt, n_cand,
-                       ia_prof_units(IA_PROF_SEARCH), (float *)nullptr, (float *)nullptr);
+  unsigned long long *const prof = ia_prof_units(IA_PROF_SEARCH);   // non-null only under ia_profile_enable
+  const int mode = with_jinv ? 2 : 1;
+#define IA_SEARCH_LAUNCH(M, PR)                                                                                                 \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search<M, PR>), grd, blk, 0, s, xd, P, n_pts_dev, voxel_J, tfs, b, n_init, g,           \
+                     cvg_thresh * cvg_thresh, dvg_thresh * dvg_thresh, (float *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr, \
+                     (float *)nullptr, cand_xc, cand_cap, pt_off, pt_cnt, n_cand, prof, M == 2 ? cand_Jinv : (float *)nullptr,   \
+                     M == 2 ? jinv_dense : (float *)nullptr)
+  if (mode == 1 && !prof) IA_SEARCH_LAUNCH(1, false);
+  else if (mode == 1) IA_SEARCH_LAUNCH(1, true);
+  else if (!prof) IA_SEARCH_LAUNCH(2, false);
+  else IA_SEARCH_LAUNCH(2, true);
+#undef IA_SEARCH_LAUNCH
   ia_prof_end(IA_PROF_SEARCH, s);
   IA_LAUNCH_CHECK("k_search<compact>");
   return IA_OK;
@@ -408,8 +421,12 @@ __global__ void k_selftest_jinv_update(const float *__restrict__ Ji, const float
   float A[9], B[9];
 #pragma unroll
   for (int k = 0; k < 9; k++) { A[k] = Ji[(size_t)i * 9 + k]; B[k] = A[k]; }
-  const bool sh = jinv_update_impl<true>(A, x[i * 3], x[i * 3 + 1], x[i * 3 + 2], g[i * 3], g[i * 3 + 1], g[i * 3 + 2]);
-  (void)jinv_update_impl<false>(B, x[i * 3], x[i * 3 + 1], x[i * 3 + 2], g[i * 3], g[i * 3 + 1], g[i * 3 + 2]);
+  JinvPairs JA, JB;
+  JA.load(A); JB.load(B);
+  const ia_f2 x01 = (ia_f2){x[i * 3], x[i * 3 + 1]}, g01 = (ia_f2){g[i * 3], g[i * 3 + 1]};
+  const bool sh = jinv_update_impl<true>(JA, x01, x[i * 3 + 2], g01, g[i * 3 + 2]);
+  (void)jinv_update_impl<false>(JB, x01, x[i * 3 + 2], g01, g[i * 3 + 2]);
+  JA.store(A); JB.store(B);
 #pragma unroll
   for (int k = 0; k < 9; k++) { out_shared[(size_t)i * 9 + k] = A[k]; out_plain[(size_t)i * 9 + k] = B[k]; }
   took_shared[i] = sh;
@@ -441,7 +458,7 @@ extern "C" int ia_selftest_jinv_update(const float *Ji, const float *x, const fl
 // resident workgroups per CU the runtime computes from them.
 extern "C" int ia_search_kernel_info(int *vgprs, int *lds_bytes, int *threads, int *workgroups_per_cu) {
   hipFuncAttributes a;
-  const void *fn = reinterpret_cast<const void *>(&k_search<1>);
+  const void *fn = reinterpret_cast<const void *>(&k_search<1, false>);
   if (hipFuncGetAttributes(&a, fn) != hipSuccess) return ia_set_error(IA_ERR_LAUNCH, "ia_search_kernel_info: hipFuncGetAttributes failed");
   int nb = 0;
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, IA_SEARCH_THREADS, 0);

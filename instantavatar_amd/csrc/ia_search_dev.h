@@ -11,8 +11,10 @@
 // J is channel-last: a corner record is 3 x float4 = 48 contiguous bytes.  A lane fetching its own 8 corners would issue 24
 // divergent 16-byte loads, each its own look-up in the CU's vector L1.  Here the four lanes of a quad serve their four
 // fetches together: the quad's 12 (target lane, row) pairs are dealt to its FOUR lanes in THREE rounds -- round R, lane k
-// serves pair 4R + k = (target (4R + k) / 3, row (4R + k) % 3): it learns the target's corner offsets and weights by DPP
-// (per-lane constant sources: quad_perm [0,0,0,1], [1,1,2,2], [2,3,3,3]), loads ITS ROW of the 8 corner records (the lanes of
+// serves pair 4R + k = (target (4R + k) / 3, row (4R + k) % 3): it learns the target's corner offsets by DPP (per-lane
+// constant sources: quad_perm [0,0,0,1], [1,1,2,2], [2,3,3,3]) and its eight weights from LDS (every lane writes its weights
+// once per step as two float4; the consumer is v_pk_fma_f32, which cannot fold a DPP operand, so the DPP form was 24 real
+// v_mov_b32_dpp per wave-step against six plain moves now -- round 7, bit-identical: the same bits travel), loads ITS ROW of the 8 corner records (the lanes of
 // a quad that serve the same target read one 48-byte record: 1-2 L1 segments instead of 3 look-ups) and accumulates it
 // over the corners in the reference order -- every output element is the same fma chain as in a lane-per-fetch kernel, on
 // another lane -- then stores the row as float4 number 4R + k of the quad's 12-float4 block in LDS, which is exactly where
@@ -28,6 +30,7 @@ struct FetchPlan {
   float w[8];
   uint32_t load;   // 1: the lane is active and at least one corner lies inside the grid
 };
+// (off and load travel by DPP, w through LDS: see fetch_round3)
 
 // Validity is folded into the six 1-D interpolation factors -- one unsigned compare and one select per axis end instead of
 // two compares per end, three-way ANDs and eight selects on the products (round 3's form).  A zeroed factor makes its four
@@ -76,15 +79,17 @@ template <int PERM> __device__ __forceinline__ float quad_perm(float v) {
 // The offset broadcast and the row-offset add are ONE v_add_u32_dpp (inline asm: left to itself the compiler emits
 // v_mov_b32_dpp + v_add_u32, because it sinks the add to the predicated loads).  The two wait states a DPP read needs after a
 // VALU write of its source are the s_nop: inline asm is opaque to the hazard recogniser.
+// s_wt: weights 0..3 of lane t at [t], weights 4..7 at [IA_WT_HALF + t] (two planes: consecutive lanes write consecutive 16 bytes)
+#define IA_WT_HALF 256   // = the workgroup size of k_search
 template <int R>
-__device__ __forceinline__ void fetch_round3(const char *__restrict__ vJb, const FetchPlan &p, float4 *__restrict__ s_quad_k) {
+__device__ __forceinline__ void fetch_round3(const char *__restrict__ vJb, const FetchPlan &p, float4 *__restrict__ s_quad_k,
+                                             const float4 *__restrict__ s_wt_r) {
   constexpr int PERM = R == 0 ? 0x40 : (R == 1 ? 0xA5 : 0xFE);
   const uint32_t load = quad_perm<PERM>(p.load);
   if (__ballot(load != 0) == 0) return;
   const uint32_t koff = (uint32_t)(((threadIdx.x & 3) + R) % 3) * 16u;   // row (4R + k) % 3 = (k + R) % 3
   // (all DPP reads before the divergent part: a source lane that sits out this round must still be enabled when it is read)
   uint32_t off[8];
-  float w[8];
   // ONE asm statement: the s_nop and the eight DPP adds cannot be separated -- volatile asm is ordered only against other
   // volatile asm, so with separate statements the compiler was free to sink a VALU producer of p.off[c] between the s_nop
   // and a DPP read (the build checked clean, nothing enforced it).  Early-clobber outputs: all eight are
@@ -96,13 +101,14 @@ __device__ __forceinline__ void fetch_round3(const char *__restrict__ vJb, const
                : "v"(p.off[0]), "v"(p.off[1]), "v"(p.off[2]), "v"(p.off[3]), "v"(p.off[4]), "v"(p.off[5]), "v"(p.off[6]), "v"(p.off[7]),
                  "v"(koff), "i"(PERM & 3), "i"((PERM >> 2) & 3), "i"((PERM >> 4) & 3), "i"((PERM >> 6) & 3));
 #undef IA_DPP_ADD
-#pragma unroll
-  for (int c = 0; c < 8; c++) w[c] = quad_perm<PERM>(p.w[c]);
   if (load != 0) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     float4 v[8];
 #pragma unroll
     for (int c = 0; c < 8; c++) v[c] = *reinterpret_cast<const float4 *>(vJb + (size_t)off[c]);
+    // the target's eight weights: two 16-byte LDS reads of what it wrote in fetch_J_quad (the same bits a DPP move would bring)
+    const float4 w03 = s_wt_r[0], w47 = s_wt_r[IA_WT_HALF];
+    const float w[8] = {w03.x, w03.y, w03.z, w03.w, w47.x, w47.y, w47.z, w47.w};
     f2 a0 = (f2){0.f, 0.f}, a1 = (f2){0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < 8; c++) {
@@ -120,9 +126,12 @@ __device__ __forceinline__ void fetch_round3(const char *__restrict__ vJb, const
 // so the result equals the reference's "skip the corner" bit for bit; a fetch with all 8 corners outside loads nothing and
 // reads zeros.
 __device__ __forceinline__ void fetch_J_quad(const float *__restrict__ vJ, const SnarfGridDev &g, float gx, float gy, float gz,
-                                             bool active, float *__restrict__ out, bool &loaded, float4 *__restrict__ s_del) {
+                                             bool active, float *__restrict__ out, bool &loaded, float4 *__restrict__ s_del,
+                                             float4 *__restrict__ s_wt) {
   FetchPlan p;
   fetch_plan(g, gx, gy, gz, active, p);
+  s_wt[threadIdx.x] = make_float4(p.w[0], p.w[1], p.w[2], p.w[3]);
+  s_wt[IA_WT_HALF + threadIdx.x] = make_float4(p.w[4], p.w[5], p.w[6], p.w[7]);
   loaded = p.load != 0;
   const int k = threadIdx.x & 3;
   const char *vJb = reinterpret_cast<const char *>(vJ);
@@ -133,9 +142,11 @@ __device__ __forceinline__ void fetch_J_quad(const float *__restrict__ vJ, const
   __builtin_amdgcn_wave_barrier();
   {
     float4 *const s_quad_k = s_del + (threadIdx.x & ~3u) * 3 + k;
-    fetch_round3<0>(vJb, p, s_quad_k);
-    fetch_round3<1>(vJb, p, s_quad_k);
-    fetch_round3<2>(vJb, p, s_quad_k);
+    // round R serves target (4R + k) / 3 of the quad: lanes 0,0,0,1 / 1,1,2,2 / 2,3,3,3
+    const float4 *const s_wt_q = s_wt + (threadIdx.x & ~3u);
+    fetch_round3<0>(vJb, p, s_quad_k, s_wt_q + k / 3);
+    fetch_round3<1>(vJb, p, s_quad_k, s_wt_q + (4 + k) / 3);
+    fetch_round3<2>(vJb, p, s_quad_k, s_wt_q + (8 + k) / 3);
   }
   __builtin_amdgcn_wave_barrier();
   {
@@ -177,36 +188,77 @@ __device__ __forceinline__ bool div_shared_range(float c0, float c1, float c2, f
   const int e_s = __builtin_amdgcn_frexp_expf(s);
   return e_hi <= 8 && e_lo >= -48 && e_s >= -66 && e_s <= 22;
 }
+// ---- the Broyden state in packed pairs --------------------------------------------------------------------------------
+// J_inv lives in four register pairs and a scalar, laid out so that the independent chains of the update sit side by side in
+// v_pk_* instructions without a register move: P = (J00, J10), Q = (J01, J11), R = (J02, J12), S = (J20, J21), J22.  Rows 0 and
+// 1 of r = -J_inv g and of u = -J_inv g are ONE packed chain (P, Q, R against a broadcast g_j), the numerators c_j t_i are
+// c_j (t0, t1) and (c0, c1) t2, and the five instructions of `div_shared` run on pairs; every element keeps the operand order
+// of IA_DOT3 / div_shared, a packed fp32 instruction rounds each half like its scalar twin, so the bits are the scalar
+// code's (`ia_selftest_jinv_update` against the compiler's divisions, tests/test_gpu_edge_cases.py).  v_div_fixup, v_rcp and
+// the range test have no packed form.  The SLP vectoriser stays off (build.py): its pairs of convenience cost moves.
+typedef float ia_f2 __attribute__((ext_vector_type(2)));
+#define IA_DOT3_2(a0, b0, a1, b1, a2, b2) __builtin_elementwise_fma((a2), (b2), __builtin_elementwise_fma((a1), (b1), (a0) * (b0)))
+__device__ __forceinline__ ia_f2 ia_dup(float v) { return (ia_f2){v, v}; }
+struct JinvPairs {
+  ia_f2 P, Q, R, S;
+  float J22;
+  __device__ __forceinline__ void load(const float *Ji) {
+    P = (ia_f2){Ji[0], Ji[3]}; Q = (ia_f2){Ji[1], Ji[4]}; R = (ia_f2){Ji[2], Ji[5]}; S = (ia_f2){Ji[6], Ji[7]}; J22 = Ji[8];
+  }
+  __device__ __forceinline__ void store(float *Ji) const {
+    Ji[0] = P.x; Ji[1] = Q.x; Ji[2] = R.x; Ji[3] = P.y; Ji[4] = Q.y; Ji[5] = R.y; Ji[6] = S.x; Ji[7] = S.y; Ji[8] = J22;
+  }
+};
+// (u0, u1), u2 = -J_inv g (fuse_cuda_kernel_fast.cu:340-347) and the r of the update below
+__device__ __forceinline__ void jinv_neg_apply(const JinvPairs &J, ia_f2 g01, float g2, ia_f2 &r01, float &r2) {
+  r01 = IA_DOT3_2(-J.P, ia_dup(g01.x), -J.Q, ia_dup(g01.y), -J.R, ia_dup(g2));
+  r2 = IA_DOT3(-J.S.x, g01.x, -J.S.y, g01.y, -J.J22, g2);
+}
+__device__ __forceinline__ ia_f2 div_shared2(ia_f2 n, float s, float rb) {
+  const ia_f2 s2 = ia_dup(s), rb2 = ia_dup(rb);
+  const ia_f2 q0 = n * rb2;
+  const ia_f2 q1 = __builtin_elementwise_fma(__builtin_elementwise_fma(-s2, q0, n), rb2, q0);
+  const ia_f2 q2 = __builtin_elementwise_fma(__builtin_elementwise_fma(-s2, q1, n), rb2, q1);
+  return (ia_f2){__builtin_amdgcn_div_fixupf(q2.x, s, n.x), __builtin_amdgcn_div_fixupf(q2.y, s, n.y)};
+}
 // fuse_J_inv_update (fuse_cuda_kernel_fast.cu:23-55).  SHARED: the shared reciprocal when EVERY lane of the wave is inside
 // the range, the compiler's divisions otherwise; returns which one ran.
 template <bool SHARED>
-__device__ __forceinline__ bool jinv_update_impl(float *Ji, float x0, float x1, float x2, float g0, float g1, float g2) {
-  const float J00 = Ji[0], J01 = Ji[1], J02 = Ji[2], J10 = Ji[3], J11 = Ji[4], J12 = Ji[5], J20 = Ji[6],
-              J21 = Ji[7], J22 = Ji[8];
-  const float c0 = IA_DOT3(J00, x0, J10, x1, J20, x2);
-  const float c1 = IA_DOT3(J01, x0, J11, x1, J21, x2);
-  const float c2 = IA_DOT3(J02, x0, J12, x1, J22, x2);
+__device__ __forceinline__ bool jinv_update_impl(JinvPairs &J, ia_f2 x01, float x2, ia_f2 g01, float g2) {
+  const float x0 = x01.x, x1 = x01.y, g0 = g01.x, g1 = g01.y;
+  // c_j = J0j x0 + J1j x1 + J2j x2: the last fma of c0 and c1 is one packed instruction on S
+  const ia_f2 c01 = __builtin_elementwise_fma(J.S, ia_dup(x2), (ia_f2){__builtin_fmaf(J.P.y, x1, J.P.x * x0), __builtin_fmaf(J.Q.y, x1, J.Q.x * x0)});
+  const float c0 = c01.x, c1 = c01.y;
+  const float c2 = IA_DOT3(J.R.x, x0, J.R.y, x1, J.J22, x2);
   const float s = IA_DOT3(c0, g0, c1, g1, c2, g2);
-  const float r0 = IA_DOT3(-J00, g0, -J01, g1, -J02, g2);
-  const float r1 = IA_DOT3(-J10, g0, -J11, g1, -J12, g2);
-  const float r2 = IA_DOT3(-J20, g0, -J21, g1, -J22, g2);
-  if (SHARED) {
-    const float t0 = r0 + x0, t1 = r1 + x1, t2 = r2 + x2;
-    if (__ballot(!div_shared_range(c0, c1, c2, t0, t1, t2, s)) == 0) {
-      const float rb = rcp_refined(s);
-      const float tt[3] = {t0, t1, t2}, cc[3] = {c0, c1, c2};
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) Ji[3 * i + j] += div_shared(cc[j] * tt[i], s, rb);
-      return true;
-    }
+  ia_f2 r01;
+  float r2;
+  jinv_neg_apply(J, g01, g2, r01, r2);
+  const ia_f2 t01 = r01 + x01;
+  const float t2 = r2 + x2;
+  // both division paths deliver the nine quotients; the one J_inv += q after the join keeps the state in its registers
+  ia_f2 qP, qQ, qR, qS;
+  float q22;
+  bool shared = false;
+  if (SHARED) shared = __ballot(!div_shared_range(c0, c1, c2, t01.x, t01.y, t2, s)) == 0;
+  if (shared) {
+    const float rb = rcp_refined(s);
+    qP = div_shared2(ia_dup(c0) * t01, s, rb);
+    qQ = div_shared2(ia_dup(c1) * t01, s, rb);
+    qR = div_shared2(ia_dup(c2) * t01, s, rb);
+    qS = div_shared2(c01 * ia_dup(t2), s, rb);
+    q22 = div_shared(c2 * t2, s, rb);
+  } else {
+    const float r0 = r01.x, r1 = r01.y;
+    qP = (ia_f2){c0 * (r0 + x0) / s, c0 * (r1 + x1) / s};
+    qQ = (ia_f2){c1 * (r0 + x0) / s, c1 * (r1 + x1) / s};
+    qR = (ia_f2){c2 * (r0 + x0) / s, c2 * (r1 + x1) / s};
+    qS = (ia_f2){c0 * (r2 + x2) / s, c1 * (r2 + x2) / s};
+    q22 = c2 * (r2 + x2) / s;
   }
-  Ji[0] += c0 * (r0 + x0) / s; Ji[1] += c1 * (r0 + x0) / s; Ji[2] += c2 * (r0 + x0) / s;
-  Ji[3] += c0 * (r1 + x1) / s; Ji[4] += c1 * (r1 + x1) / s; Ji[5] += c2 * (r1 + x1) / s;
-  Ji[6] += c0 * (r2 + x2) / s; Ji[7] += c1 * (r2 + x2) / s; Ji[8] += c2 * (r2 + x2) / s;
-  return false;
+  J.P += qP; J.Q += qQ; J.R += qR; J.S += qS; J.J22 += q22;
+  return shared;
 }
-__device__ __forceinline__ void jinv_update(float *Ji, float x0, float x1, float x2, float g0, float g1, float g2) {
-  (void)jinv_update_impl<true>(Ji, x0, x1, x2, g0, g1, g2);
+__device__ __forceinline__ void jinv_update(JinvPairs &J, ia_f2 x01, float x2, ia_f2 g01, float g2) {
+  (void)jinv_update_impl<true>(J, x01, x2, g01, g2);
 }
