@@ -1,0 +1,72 @@
+"""Write the avatar's geometry as triangle meshes: the canonical mesh and, with a pose track, one posed mesh per frame.
+
+    python -m instantavatar_amd.drivers.extract_mesh --ckpt checkpoints/last.ckpt --smpl-dir ./data/SMPLX/smpl --gender male \\
+        --betas data/subject/anim_nerf_train.npz --poses data/animation/aist_demo.npz --max-frames 8 --out meshes/subject
+    python -m instantavatar_amd.drivers.extract_mesh --synthetic --resolution 128 --out /tmp/mesh
+
+The canonical mesh is the isosurface sigma = --level of the canonical density field by marching tetrahedra on a
+--resolution^3 lattice over the field's box (`AvatarModel.extract_mesh`; DESIGN.md section 4, "isosurface"); the level is this
+project's choice, the reference has none.  Posed meshes are the same vertices skinned forward with the frame's bone
+transforms (`AvatarModel.pose_mesh`), in the world frame of the animate driver's camera; they share faces and colours with
+the canonical mesh.  Files: `canonical.<format>`, `posed_<i>.<format>`."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+from . import animate
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--poses", help="npz with `poses` [n,>=72] and `trans` [n,3]: also write posed_<i> per frame")
+    ap.add_argument("--ckpt", help="Lightning checkpoint of DNeRFModel")
+    ap.add_argument("--betas", help="npz with `betas` (the subject's anim_nerf_train.npz)")
+    ap.add_argument("--smpl-dir", default="./data/SMPLX/smpl")
+    ap.add_argument("--gender", default="neutral")
+    ap.add_argument("--confs", default=os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "confs"))
+    ap.add_argument("--deformer", default="fast_snarf")
+    ap.add_argument("--network", default="ngp")
+    ap.add_argument("--renderer", default="raymarcher_acc")
+    ap.add_argument("--synthetic", action="store_true", help="synthetic SMPL-like body + field (no SMPL pickle / checkpoint needed)")
+    ap.add_argument("--seed", type=int, default=None, help="--synthetic: seed of the synthetic body + field")
+    ap.add_argument("--max-frames", type=int, default=0)
+    ap.add_argument("--resolution", type=int, default=256, help="lattice samples per axis (2 .. 564)")
+    ap.add_argument("--level", type=float, default=10.0, help="density of the isosurface (this project's choice; the reference has none)")
+    ap.add_argument("--keep", choices=("largest", "all"), default="largest", help="largest: only the connected component with the largest area")
+    ap.add_argument("--format", choices=("ply", "obj"), default="ply")
+    ap.add_argument("--out", default="meshes/out")
+    args = ap.parse_args(argv)
+    if not args.synthetic and not args.ckpt:
+        ap.error("--ckpt is required unless --synthetic is given")
+    import torch
+    device = torch.device("cuda:0")
+    model, betas = animate.build_model(args, device)
+    model.eval()
+    os.makedirs(args.out, exist_ok=True)
+    write = lambda mesh, name: getattr(mesh, "to_" + args.format)(os.path.join(args.out, "%s.%s" % (name, args.format)))
+    timings = {}
+    mesh = model.extract_mesh(resolution=args.resolution, level=args.level, largest=args.keep == "largest", timings=timings)
+    write(mesh, "canonical")
+    print("canonical mesh: %d vertices, %d faces at resolution %d, level %g (field %.3f s, count + emit %.3f s, component filter %.3f s)"
+          % (mesh.verts.shape[0], mesh.faces.shape[0], args.resolution, args.level, timings["field"], timings["isosurface"], timings["component"]))
+    n = 0
+    if args.poses:
+        z = np.load(args.poses)
+        poses, trans = z["poses"].astype(np.float32), z["trans"].astype(np.float32)
+        if args.max_frames:
+            poses, trans = poses[:args.max_frames], trans[:args.max_frames]
+        seq = animate.AnimateSequence(poses, trans, betas, device, size=8)      # (its SMPL parameters; the rays are not used)
+        t0 = time.perf_counter()
+        for i in range(len(seq)):
+            write(model.pose_mesh(mesh, seq.batch(i, rays=False)), "posed_%d" % i)
+        n = len(seq)
+        print("posed meshes: %d frames in %.3f s (file writing included)" % (n, time.perf_counter() - t0))
+    print("wrote canonical.%s%s to %s" % (args.format, " and %d posed meshes" % n if n else "", args.out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

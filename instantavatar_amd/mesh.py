@@ -1,0 +1,196 @@
+"""Triangle meshes of the avatar: the isosurface of the canonical density field by marching tetrahedra on the GPU
+(csrc/ia_isosurface.hip, include/instantavatar_hip_mesh.h; definition in DESIGN.md section 4, "isosurface"), its largest
+connected component, per-vertex colours and normals from the field, forward skinning into a posed frame, and PLY / OBJ
+writers (numpy only).  `AvatarModel.extract_mesh` / `AvatarModel.pose_mesh` are the public entry points.
+
+The level is OURS: the reference ships a marching-cubes helper it never calls, whose default level 0 is meant for signed
+distances; sigma = 10 is a density at which a 1 cm step is already ~10 % opaque.  It is a parameter."""
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+
+DEFAULT_LEVEL = 10.0
+
+
+class Mesh:
+    """verts [nv,3] fp32, faces [nf,3] int32, normals [nv,3] fp32 (unit length or zero), colors [nv,3] fp32 in [0, 1] in the
+    MODEL's channel order (B, G, R: the cv2.imread order of the training images) -- device tensors."""
+
+    def __init__(self, verts, faces, normals, colors):
+        self.verts, self.faces, self.normals, self.colors = verts, faces, normals, colors
+
+    def _host(self):
+        f = lambda t: t.detach().cpu().numpy()
+        rgb = f(self.colors).astype(np.float32)[:, ::-1]          # model order -> RGB, as drivers/animate.write_frames
+        rgb8 = (np.clip(rgb, np.float32(0), np.float32(1)) * np.float32(255)).astype(np.uint8)   # quantised as ia_pack_rgba8
+        return f(self.verts).astype("<f4"), f(self.faces).astype("<i4"), f(self.normals).astype("<f4"), rgb8
+
+    def to_ply(self, path):
+        """binary little-endian PLY: vertex = float x y z nx ny nz, uchar red green blue; face = list uchar int32"""
+        v, f, n, c = self._host()
+        vert = np.empty(len(v), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                                       ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+        for k, name in enumerate(("x", "y", "z")):
+            vert[name] = v[:, k]
+            vert["n" + name] = n[:, k]
+        vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
+        face = np.empty(len(f), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        face["n"] = 3
+        face["v"] = f
+        header = ("ply\nformat binary_little_endian 1.0\ncomment instantavatar_amd mesh\nelement vertex %d\n"
+                  "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\n"
+                  "property list uchar int vertex_indices\nend_header\n" % (len(v), len(f)))
+        with open(path, "wb") as out:
+            out.write(header.encode("ascii"))
+            out.write(vert.tobytes())
+            out.write(face.tobytes())
+
+    def to_obj(self, path):
+        """Wavefront OBJ: `v x y z r g b` (colours in [0, 1], 8-bit steps), `vn`, `f a//a b//b c//c` (1-based)"""
+        v, f, n, c = self._host()
+        with open(path, "w") as out:
+            out.write("# instantavatar_amd mesh: %d vertices, %d faces\n" % (len(v), len(f)))
+            np.savetxt(out, np.concatenate([v.astype(np.float64), c.astype(np.float64) / 255.0], 1), fmt="v %.9g %.9g %.9g %.6g %.6g %.6g")
+            np.savetxt(out, n.astype(np.float64), fmt="vn %.9g %.9g %.9g")
+            g = f.astype(np.int64) + 1
+            np.savetxt(out, np.stack([g[:, 0], g[:, 0], g[:, 1], g[:, 1], g[:, 2], g[:, 2]], 1), fmt="f %d//%d %d//%d %d//%d")
+
+
+def field_box(net):
+    """(lo, hi) fp32 [3] of the box the field normalises to the unit cube: center -/+ scale / 2, formed in fp32"""
+    center, scale = (np.asarray(t, np.float32) for t in net._center_scale_host())
+    half = scale / np.float32(2)
+    return center - half, center + half
+
+
+def lattice_desc(N, lo, hi):
+    d = _lib.OccGrid()
+    d.G = int(N)
+    d.aabb_min[:], d.aabb_max[:] = [float(x) for x in lo], [float(x) for x in hi]
+    return d
+
+
+def lattice_sigma(net, lat, chunk=1 << 21):
+    """sigma [N^3] of `net` (ia_field_fwd, canonical space, no deformer) on the lattice, evaluated `chunk` points at a time"""
+    N = lat.G
+    n = N ** 3
+    dev = net.center.device
+    chunk = max(1, min(int(chunk), n))
+    sigma = torch.empty(n, device=dev)
+    pts, rgb = torch.empty((chunk, 3), device=dev), torch.empty((chunk, 3), device=dev)
+    for first in range(0, n, chunk):
+        count = min(chunk, n - first)
+        _lib.call("ia_iso_lattice_points", lat, first, count, pts)
+        _lib.call("ia_field_fwd", pts, count, None, net.field_desc(count), rgb, sigma[first:first + count])
+    return sigma
+
+
+def isosurface(sigma, lat, level=DEFAULT_LEVEL, cap=True):
+    """marching tetrahedra on a device lattice sigma [N^3] -> (verts [nv,3] fp32, faces [nf,3] int32).  One host read: the two counts."""
+    _lib.require_cuda(sigma)
+    N = lat.G
+    sigma = sigma.detach().reshape(-1).float().contiguous()
+    if sigma.numel() != N ** 3:
+        raise _lib.IAError("isosurface: %d samples for a lattice of %d^3" % (sigma.numel(), N))
+    dev = sigma.device
+    nb = int(_lib.call("ia_iso_workspace_bytes", N))
+    if nb == 0:
+        raise _lib.IAError("isosurface: resolution %d outside [2, 564]" % N)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.call("ia_iso_count", sigma, N, float(level), int(bool(cap)), ws, nb, counts)
+    nv, nf = counts.tolist()
+    verts, faces = torch.empty((nv, 3), device=dev), torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    _lib.call("ia_iso_emit", sigma, lat, float(level), int(bool(cap)), ws, nb, verts, nv, faces, nf)
+    return verts, faces
+
+
+def largest_component(verts, faces, area_unit):
+    """-> (verts, faces, vert_src [nv_out] int32) of the component with the largest surface area; order preserved"""
+    _lib.require_cuda(verts, faces)
+    nv, nf = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    nb = int(_lib.call("ia_mesh_component_workspace_bytes", nv, nf))
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.call("ia_mesh_largest_count", verts, faces, nv, nf, float(area_unit), ws, nb, counts)
+    nv2, nf2 = counts.tolist()
+    v2, f2 = torch.empty((nv2, 3), device=dev), torch.empty((nf2, 3), dtype=torch.int32, device=dev)
+    src = torch.empty(nv2, dtype=torch.int32, device=dev)
+    _lib.call("ia_mesh_largest_emit", verts, faces, nv, nf, ws, nb, v2, nv2, f2, nf2, src)
+    return v2, f2, src
+
+
+def box_area_unit(lo, hi):
+    """the largest face area of the box: the unit of the component filter's fixed-point areas"""
+    e = np.asarray(hi, np.float64) - np.asarray(lo, np.float64)
+    return float(max(e[0] * e[1], e[1] * e[2], e[0] * e[2]))
+
+
+@torch.no_grad()
+def extract(net, resolution=256, level=DEFAULT_LEVEL, largest=True, cap=True, chunk=1 << 21, timings=None):
+    """The canonical mesh of the field `net` (NeRFNGPNet): `AvatarModel.extract_mesh`.
+    timings: a dict that receives the wall time in seconds of `field` (lattice sigma), `isosurface` (count + emit),
+    `component` (the filter) and `attributes` (colours, normals); measuring synchronises after every stage."""
+    _lib.require_cuda(net.center)
+    clock = None
+    if timings is not None:
+        def clock(name, t0):
+            torch.cuda.synchronize()
+            timings[name] = time.perf_counter() - t0
+            return time.perf_counter()
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    lo, hi = field_box(net)
+    lat = lattice_desc(resolution, lo, hi)
+    sigma = lattice_sigma(net, lat, chunk)
+    if clock:
+        t0 = clock("field", t0)
+    verts, faces = isosurface(sigma, lat, level, cap)
+    del sigma
+    if clock:
+        t0 = clock("isosurface", t0)
+    if largest:
+        verts, faces, _ = largest_component(verts, faces, box_area_unit(lo, hi))
+    if clock:
+        t0 = clock("component", t0)
+    nv = verts.shape[0]
+    dev = verts.device
+    colors, normals = torch.empty((nv, 3), device=dev), torch.empty((nv, 3), device=dev)
+    if nv:
+        sig, grad = torch.empty(nv, device=dev), torch.empty((nv, 3), device=dev)
+        _lib.call("ia_field_fwd", verts, nv, None, net.field_desc(nv), colors, sig)
+        _lib.call("ia_field_sigma_grad", verts, nv, None, net.field_desc(), sig, grad)
+        _lib.call("ia_unit_negative", grad, nv, normals)
+    if clock:
+        clock("attributes", t0)
+    return Mesh(verts, faces, normals, colors)
+
+
+@torch.no_grad()
+def pose(deformer, mesh, batch):
+    """The canonical `mesh` in the frame of `batch` (SMPL parameters): `AvatarModel.pose_mesh`.  Positions by forward
+    skinning (ia_forward_skin), normals by ia_normals_from_gradient with one "ray" per vertex; faces and colours are shared."""
+    from .deformers.snarf_deformer import SNARFDeformer
+    if not isinstance(deformer, SNARFDeformer):
+        raise NotImplementedError("pose_mesh is implemented for the SNARF deformer (deformers.snarf_deformer.SNARFDeformer), whose "
+                                  "transform grid forward skinning reads; SMPLDeformer has none")
+    _lib.require_cuda(mesh.verts)
+    deformer.prepare_deformer(batch, want_bbox=False)
+    nv = mesh.verts.shape[0]
+    dev = mesh.verts.device
+    verts = mesh.verts.detach().float().contiguous()
+    s2w = deformer.A.detach().reshape(-1, 4, 4)[0].float().contiguous()
+    w2s = deformer.w2s.detach().reshape(4, 4).float().contiguous()
+    xd, normals = torch.empty((nv, 3), device=dev), torch.zeros((nv, 3), device=dev)
+    if nv:
+        vJ, grid = deformer.deformer.voxel_J_cl, deformer.deformer.grid_desc()
+        _lib.call("ia_forward_skin", verts, nv, vJ, grid, s2w, xd)
+        # n = -M^{-T} g with g = -n_c: only the direction of the gradient enters
+        idx = torch.arange(nv, dtype=torch.int32, device=dev)
+        _lib.call("ia_normals_from_gradient", verts, (-mesh.normals).contiguous(), idx, nv, None, vJ, grid, w2s, nv, normals)
+    return Mesh(xd, mesh.faces, normals, mesh.colors)

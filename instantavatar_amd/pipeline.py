@@ -67,6 +67,21 @@ class AvatarModel(torch.nn.Module):
         nrm = self.renderer.render_normals(rays, self.deformer, self.net_coarse, d["depth_coarse"], d["alpha_coarse"])
         return rgb, depth, alpha, counter, nrm.reshape(-1, *img_size, 3)
 
+    def extract_mesh(self, resolution=256, level=10.0, largest=True, cap=True, chunk=1 << 21, timings=None):
+        """The avatar's canonical geometry as a triangle mesh (`mesh.Mesh`: verts, faces, normals, colors on the device): the
+        isosurface sigma = `level` of the canonical field by marching tetrahedra on a `resolution`^3 lattice over the field's box
+        ("isosurface").  largest: keep the connected component with the largest area only; cap: count the
+        outermost lattice layer as empty, which closes the surface at the box wall; chunk: lattice points per field call (the
+        result does not depend on it).  The level is this project's choice, not the reference's (see `mesh`)."""
+        from . import mesh
+        return mesh.extract(self.net_coarse, resolution, level, largest, cap, chunk, timings)
+
+    def pose_mesh(self, mesh, batch):
+        """`mesh` (canonical, from `extract_mesh`) skinned forward into the frame of `batch` (its SMPL parameters), in the world
+        frame; normals are transformed with it, faces and colours are shared.  SNARF deformer only."""
+        from . import mesh as mesh_mod
+        return mesh_mod.pose(self.deformer, mesh, batch)
+
 
 class GraphedRenderer:
     """render_image_fast replayed from a HIP graph (torch.cuda.CUDAGraph).
