@@ -143,7 +143,9 @@ def test_smpl_deformer_prepare_three_routes_values_and_gradients(blend):
       library    SMPL.forward with the library GEMMs / einsum of the reference's lbs.py, under autograd
     T_inv, posed vertices, w2s, the template bounding box, and the gradients of a random functional of T_inv AND w2s (the ray
     frame: transform_rays_w2s is differentiable in the reference) w.r.t. betas, body pose, root orientation and translation.
-    With zero blend shapes the betas / pose-offset terms of these gradients vanish; on the blend-shape body they do not."""
+    With zero blend shapes the betas / pose-offset terms of these gradients vanish; on the blend-shape body they do not.
+    The kernels themselves are held per element and per joint to a float64 reference in tests/test_gpu_smpl_kernels.py; this test
+    checks the Python routes."""
     from instantavatar_amd.deformers import smpl_deformer as sdm
     from instantavatar_amd.deformers.smpl_deformer import SMPLDeformer
     body = syn.make_body(blendshapes=blend)

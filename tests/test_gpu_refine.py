@@ -325,7 +325,8 @@ def test_refine_step_replays_from_a_hip_graph():
 def test_smpl_chain_backward_kernel_equals_autograd_through_lbs():
     """`ia_smpl_tfs_bwd` (the kinematic chain, the inverse of the root transform and Rodrigues' formula differentiated by
     hand, one launch) against autograd through the lbs.py-style torch ops (the reference's route, ~370 launches): the same
-    upstream gradient d tfs -> the same gradients of the SMPL tables; and tfs itself from the kernel vs the torch ops."""
+    upstream gradient d tfs -> the same gradients of the SMPL tables; and tfs itself from the kernel vs the torch ops.
+    The kernels themselves are held per joint to a float64 reference in tests/test_gpu_smpl_kernels.py; this test checks the Python route."""
     from instantavatar_amd.deformers import snarf_deformer as sd
     res = {}
     for fused in (True, False):
