@@ -51,6 +51,7 @@ class AnimateSequence:
             H, W = H // downscale, W // downscale
             K[:2] /= downscale
         self.H, self.W = H, W
+        self.K = K
         o, d = make_rays(K, np.eye(4), H, W)
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=device)
         self.rays_o, self.rays_d = t(o)[None], t(d)[None]
@@ -60,6 +61,12 @@ class AnimateSequence:
 
     def __len__(self):
         return self.transl.shape[0]
+
+    def camera(self, near=0.05):
+        """the sequence's camera for the mesh rasteriser (`raster.Camera`): its K, w2c = I, its image size -- the camera its rays
+        were made from, so a raster frame overlays a rendered one"""
+        from ..raster import Camera
+        return Camera(self.K, torch.eye(4, device=self.rays_o.device), self.H, self.W, near=near)
 
     def batch(self, idx, rays=True):
         """rays=False: the SMPL parameters only (views, no launch) -- all a captured frame graph reads per frame; its rays
@@ -107,13 +114,13 @@ def _bgra_to_rgba(f):
     return np.ascontiguousarray(np.asarray(f)[..., [2, 1, 0, 3]])
 
 
-def write_frames(frames, out_dir, gif=None, indices=None, workers=8):
+def write_frames(frames, out_dir, gif=None, indices=None, workers=8, prefix=""):
     """8-bit [H, W, 4] frames in the MODEL's channel order -> `<i>.png` (+ optionally one GIF) with the colours the reference's
     files have.  The reference writes with cv2.imwrite (animate.py:113), which takes channel 0 as BLUE: the model's channels are
     in the (B, G, R) order of the cv2.imread training images (peoplesnapshot.py:100), so its files hold the intended colours;
     for the GIF it converts BGRA -> RGBA first (:115).  PIL takes channel 0 as RED: the same reorder serves both.
     indices: the file number of every frame (a rank of a multi-GPU job writes only the frames it rendered); PNG encoding
-    runs on `workers` threads (zlib releases the GIL)."""
+    runs on `workers` threads (zlib releases the GIL).  prefix: `<prefix><i>.png` (the mesh previews)."""
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
@@ -121,7 +128,7 @@ def write_frames(frames, out_dir, gif=None, indices=None, workers=8):
 
     def one(job):
         i, f = job
-        Image.fromarray(_bgra_to_rgba(f), "RGBA").save(os.path.join(out_dir, "%d.png" % i))
+        Image.fromarray(_bgra_to_rgba(f), "RGBA").save(os.path.join(out_dir, "%s%d.png" % (prefix, i)))
     with ThreadPoolExecutor(max_workers=max(1, workers)) as ex:
         list(ex.map(one, zip(indices, frames)))
     if gif and len(frames):
@@ -282,6 +289,38 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
     return res
 
 
+def mesh_preview(model, seq, out_dir, resolution, launch=None, log=print):
+    """`--mesh-preview`: the canonical mesh is extracted ONCE at lattice `resolution`; every frame is then one forward skinning
+    (`pose_mesh`) plus the raster launches (`Mesh.render`) under the sequence's camera, written as `mesh_<i>.png` (vertex colours,
+    alpha = covered).  Frames are dealt to the ranks as render_sequence deals them.  Returns a dict like render_sequence's."""
+    from .launch import Launch
+    from ..parallel import shard_frames
+    launch = launch or Launch(device=seq.rays_o.device)
+    mine = shard_frames(len(seq), launch.rank, launch.world_size)
+    cam = seq.camera()
+    dev = seq.rays_o.device
+    t0 = time.perf_counter()
+    mesh = model.extract_mesh(resolution=resolution)
+    torch.cuda.synchronize()
+    extract_s = time.perf_counter() - t0
+    host = torch.empty((len(mine), seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=dev.type == "cuda")
+    t0 = time.perf_counter()
+    for j, i in enumerate(mine):
+        host[j].copy_(model.pose_mesh(mesh, seq.batch(i, rays=False)).render(cam)["rgba8"], non_blocking=True)
+    torch.cuda.synchronize()
+    render_s = time.perf_counter() - t0
+    write_frames(host.numpy(), out_dir, indices=mine, prefix="mesh_")
+    slowest = launch.max_over_ranks(render_s)
+    launch.barrier()
+    res = dict(frames=len(seq), local=len(mine), render_s=render_s, extract_s=extract_s, frames_per_sec=(len(seq) / slowest if slowest > 0 else 0.0),
+               vertices=int(mesh.verts.shape[0]), faces=int(mesh.faces.shape[0]))
+    if log is not None and launch.is_main:
+        log("mesh preview: %d vertices, %d faces at lattice %d (extracted once in %.3f s); %d frames (%dx%d) in %.3f s = %.1f frames/s "
+            "(%d rank(s); pose_mesh + rasteriser + copy to the host, PNG I/O excluded)" % (res["vertices"], res["faces"], resolution, extract_s,
+                                                                                          res["frames"], seq.W, seq.H, slowest, res["frames_per_sec"], launch.world_size))
+    return res
+
+
 def add_launch_args(ap):
     ap.add_argument("--in-flight", type=int, default=3, help="frames in flight per GPU (captured HIP graphs replayed round-robin on their own streams)")
     ap.add_argument("--normals", action="store_true",
@@ -314,6 +353,9 @@ def main(argv=None):
                     "the WHOLE sequence of subject r (r modulo the list) with that subject's weights into its `out` -- independent "
                     "replicas, no frame sharding, no data-path collective")
     ap.add_argument("--seed", type=int, default=None, help="--synthetic: seed of the synthetic body + field (another seed = another subject)")
+    ap.add_argument("--mesh-preview", type=int, default=0, metavar="RES",
+                    help="instead of the volumetric frames: extract the canonical mesh once at lattice RES, then per frame pose it and "
+                         "rasterise it under the same camera -> mesh_<i>.png; SNARF deformer only")
     add_launch_args(ap)
     args = ap.parse_args(argv)
     from .launch import Launch
@@ -351,6 +393,13 @@ def main(argv=None):
         if args.max_frames:
             poses, trans = poses[:args.max_frames], trans[:args.max_frames]
         seq = AnimateSequence(poses, trans, betas, device, args.downscale, size=args.size or None)
+        if args.mesh_preview:
+            if replica is not None:
+                ap.error("--mesh-preview does not combine with --subjects")
+            res = mesh_preview(model, seq, args.out, args.mesh_preview, launch=launch)
+            if launch.is_main:
+                print("wrote %d mesh previews (%dx%d) to %s" % (res["frames"], seq.W, seq.H, args.out))
+            return 0
         jitter = None if args.jitter_seed is None else fixed_jitter(args.jitter_seed, device)
         res = render_sequence(model, seq, args.out, gif=None if args.no_gif else "animation.gif", launch=replica or launch,
                               in_flight=args.in_flight, jitter=jitter, log=None if replica else print, normals=args.normals)

@@ -8,7 +8,14 @@ The canonical mesh is the isosurface sigma = --level of the canonical density fi
 --resolution^3 lattice over the field's box (`AvatarModel.extract_mesh`; DESIGN.md section 4, "isosurface"); the level is this
 project's choice, the reference has none.  Posed meshes are the same vertices skinned forward with the frame's bone
 transforms (`AvatarModel.pose_mesh`), in the world frame of the animate driver's camera; they share faces and colours with
-the canonical mesh.  Files: `canonical.<format>`, `posed_<i>.<format>`."""
+the canonical mesh.  Files: `canonical.<format>`, `posed_<i>.<format>`.
+
+--render SIZE also draws the meshes with the GPU rasteriser ("rasteriser"), SIZE x SIZE pixels:
+`canonical_front.png` is the canonical mesh seen by a camera on the -z side of the field's box, on the axis through the box
+centre, looking along +z at the centre with world +y up in the image, focal length SIZE pixels, at the distance at which the
+box's nearest face spans 90 % of the image (`raster.look_at_box`); with --poses, `posed_<i>.png` (vertex colours) and
+`posed_shaded_<i>.png` (lit from the camera) show every posed mesh under the animate driver's camera scaled to SIZE.  Alpha is
+the raster mask."""
 import argparse
 import os
 import sys
@@ -37,6 +44,7 @@ def main(argv=None):
     ap.add_argument("--level", type=float, default=10.0, help="density of the isosurface (this project's choice; the reference has none)")
     ap.add_argument("--keep", choices=("largest", "all"), default="largest", help="largest: only the connected component with the largest area")
     ap.add_argument("--format", choices=("ply", "obj"), default="ply")
+    ap.add_argument("--render", type=int, default=0, metavar="SIZE", help="also write SIZE x SIZE pictures of the meshes (GPU rasteriser)")
     ap.add_argument("--out", default="meshes/out")
     args = ap.parse_args(argv)
     if not args.synthetic and not args.ckpt:
@@ -52,17 +60,33 @@ def main(argv=None):
     write(mesh, "canonical")
     print("canonical mesh: %d vertices, %d faces at resolution %d, level %g (field %.3f s, count + emit %.3f s, component filter %.3f s)"
           % (mesh.verts.shape[0], mesh.faces.shape[0], args.resolution, args.level, timings["field"], timings["isosurface"], timings["component"]))
+    if args.render:
+        from PIL import Image
+        from .. import mesh as mesh_mod, raster
+        cam = raster.look_at_box(*mesh_mod.field_box(model.net_coarse), args.render, device)
+        front = mesh.render(cam)["rgba8"].cpu().numpy()
+        Image.fromarray(animate._bgra_to_rgba(front), "RGBA").save(os.path.join(args.out, "canonical_front.png"))
     n = 0
     if args.poses:
         z = np.load(args.poses)
         poses, trans = z["poses"].astype(np.float32), z["trans"].astype(np.float32)
         if args.max_frames:
             poses, trans = poses[:args.max_frames], trans[:args.max_frames]
-        seq = animate.AnimateSequence(poses, trans, betas, device, size=8)      # (its SMPL parameters; the rays are not used)
+        seq = animate.AnimateSequence(poses, trans, betas, device, size=args.render or 8)      # (its SMPL parameters; its camera with --render)
+        cam = seq.camera() if args.render else None
+        colour, shaded = [], []
         t0 = time.perf_counter()
         for i in range(len(seq)):
-            write(model.pose_mesh(mesh, seq.batch(i, rays=False)), "posed_%d" % i)
+            posed = model.pose_mesh(mesh, seq.batch(i, rays=False))
+            write(posed, "posed_%d" % i)
+            if cam is not None:
+                img = posed.render(cam)
+                colour.append(img["rgba8"].cpu().numpy())
+                shaded.append(img["shaded8"].cpu().numpy())
         n = len(seq)
+        if cam is not None:
+            animate.write_frames(colour, args.out, prefix="posed_")
+            animate.write_frames(shaded, args.out, prefix="posed_shaded_")
         print("posed meshes: %d frames in %.3f s (file writing included)" % (n, time.perf_counter() - t0))
     print("wrote canonical.%s%s to %s" % (args.format, " and %d posed meshes" % n if n else "", args.out))
     return 0

@@ -22,6 +22,12 @@ class Mesh:
     def __init__(self, verts, faces, normals, colors):
         self.verts, self.faces, self.normals, self.colors = verts, faces, normals, colors
 
+    def render(self, camera, light=None, cull=True):
+        """8-bit pictures of the mesh under `camera` (`raster.Camera`) by the GPU rasteriser: a dict of device tensors rgba8,
+        normal8, shaded8 [H,W,4] uint8, depth [H,W], mask [H,W] (and face_id) -- see `raster.render`."""
+        from . import raster
+        return raster.render(self, camera, light, cull)
+
     def _host(self):
         f = lambda t: t.detach().cpu().numpy()
         rgb = f(self.colors).astype(np.float32)[:, ::-1]          # model order -> RGB, as drivers/animate.write_frames

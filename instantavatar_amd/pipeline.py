@@ -82,6 +82,17 @@ class AvatarModel(torch.nn.Module):
         from . import mesh as mesh_mod
         return mesh_mod.pose(self.deformer, mesh, batch)
 
+    def render_mesh(self, mesh, batch_or_camera, light=None, cull=True):
+        """Pictures of `mesh` by the GPU rasteriser (`Mesh.render`: rgba8, normal8, shaded8, depth, mask on the device).  Given a
+        `raster.Camera` the mesh is rendered as it is; given a batch (SMPL parameters plus the key "camera") the canonical mesh is
+        posed into the batch's frame first (`pose_mesh`), so the picture overlays `render_image_fast` of the same batch."""
+        from . import raster
+        if isinstance(batch_or_camera, raster.Camera):
+            return mesh.render(batch_or_camera, light, cull)
+        if "camera" not in batch_or_camera:
+            raise KeyError("render_mesh: a batch needs the key \"camera\" (a raster.Camera, e.g. AnimateSequence.camera())")
+        return self.pose_mesh(mesh, batch_or_camera).render(batch_or_camera["camera"], light, cull)
+
 
 class GraphedRenderer:
     """render_image_fast replayed from a HIP graph (torch.cuda.CUDAGraph).
