@@ -71,6 +71,9 @@ RASTER_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hi
 # and the keypoint-refinement entry points (csrc/ia_keypoints.hip): `keypoints_declarations`
 KEYPOINTS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_keypoints.h")
 
+# and the soft-silhouette entry points (csrc/ia_silhouette.hip): `silhouette_declarations`
+SILHOUETTE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_silhouette.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -226,6 +229,23 @@ def keypoints_declarations():
     return _keypoints_decls
 
 
+_silhouette_decls = None
+
+
+def silhouette_declarations():
+    """parse_header of include/instantavatar_hip_silhouette.h, read once: a seventh table, bound in `lib()` and reachable through
+    `call` like the other six; its names are disjoint from theirs."""
+    global _silhouette_decls
+    if _silhouette_decls is None:
+        d = _parse_file(SILHOUETTE_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_silhouette.h declares %s, which another header declares already" % ", ".join(both))
+        _silhouette_decls = d
+    return _silhouette_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -264,7 +284,8 @@ def lib():
                     "(`python -m instantavatar_amd.build`), or set IA_ALLOW_STALE_LIB=1 to run it anyway." % (LIB_PATH, ", ".join(diff)))
         l = C.CDLL(LIB_PATH)
         for name, d in list(declarations().items()) + list(io_declarations().items()) + list(normals_declarations().items()) \
-                + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()):
+                + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()) \
+                + list(silhouette_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -352,7 +373,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

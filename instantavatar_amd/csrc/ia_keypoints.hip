@@ -18,10 +18,13 @@
 //             k_kp_reduce_v     partials summed over the vertex blocks in block order
 //             k_kp_chain_bwd    one wave per frame: the chain reversed, Rodrigues backward -> d pose, d transl, the frame's d betas
 //             k_kp_reduce_f     d betas summed over the frames in frame order
+//   adjoint   ia_sil_body_bwd (include/instantavatar_hip_silhouette.h): the same backward for a vertex cotangent handed in by the
+//             caller -- k_kp_vertex_bwd<true> reads d vert[f,v] instead of forming it, d point is zero-filled, the rest is shared
 // fp32 with explicit operation order (-ffp-contract=off), every sum in a fixed order, no atomics.
 #include "ia_common.h"
 #include "ia_smpl_dev.h"
 #include "../../include/instantavatar_hip_keypoints.h"
+#include "../../include/instantavatar_hip_silhouette.h"
 
 #define KP_THREADS 256
 #define KP_FT 4             // frames per tile of the vertex kernels
@@ -277,6 +280,8 @@ __device__ __forceinline__ void kp_unit_diff(const float *a, const float *b, flo
   if (n > 0.f) { acc[0] += s * (d0 / n); acc[1] += s * (d1 / n); acc[2] += s * (d2 / n); }
 }
 
+// GIVEN: `verts` holds the caller's d vert [F,V,3] (ia_sil_body_bwd) and kp_vertex is not read
+template <bool GIVEN>
 __global__ __launch_bounds__(KP_THREADS) void k_kp_vertex_bwd(KpBodyDev B, const float *__restrict__ betas, int F, int n_vb, KpWs w,
                                                                const float *__restrict__ verts, const int32_t *__restrict__ kp_vertex) {
   __shared__ float sA[KP_FT][288], spf[KP_FT][KP_PF];
@@ -285,10 +290,12 @@ __global__ __launch_bounds__(KP_THREADS) void k_kp_vertex_bwd(KpBodyDev B, const
   __shared__ int skv[IA_KP_N_VERTEX];
   const int tid = threadIdx.x, f0 = (int)(blockIdx.x / n_vb) * KP_FT, vb = blockIdx.x % n_vb, v0 = vb * KP_THREADS, V = B.V;
   kp_load_tile(w, f0, F, sA, spf);
-  if (tid < IA_KP_N_VERTEX) skv[tid] = kp_vertex[tid];
-  for (int i = tid; i < KP_FT * IA_KP_N_VERTEX * 3; i += KP_THREADS) {
-    const int fi = i / (IA_KP_N_VERTEX * 3), r = i % (IA_KP_N_VERTEX * 3);
-    sdpt[fi][r / 3][r % 3] = f0 + fi < F ? w.dpoint[((size_t)(f0 + fi) * IA_KP_N_POINTS + 24) * 3 + r] : 0.f;
+  if (!GIVEN) {
+    if (tid < IA_KP_N_VERTEX) skv[tid] = kp_vertex[tid];
+    for (int i = tid; i < KP_FT * IA_KP_N_VERTEX * 3; i += KP_THREADS) {
+      const int fi = i / (IA_KP_N_VERTEX * 3), r = i % (IA_KP_N_VERTEX * 3);
+      sdpt[fi][r / 3][r % 3] = f0 + fi < F ? w.dpoint[((size_t)(f0 + fi) * IA_KP_N_POINTS + 24) * 3 + r] : 0.f;
+    }
   }
   __syncthreads();
   // phase A, one thread per vertex: d vert, vs + po and T.R^T d vert of the tile's frames into LDS
@@ -303,10 +310,14 @@ __global__ __launch_bounds__(KP_THREADS) void k_kp_vertex_bwd(KpBodyDev B, const
       float dv[3] = {0.f, 0.f, 0.f}, vp[3] = {0.f, 0.f, 0.f}, dvp[3] = {0.f, 0.f, 0.f};
       if (f < F) {
         const float *x = verts + ((size_t)f * V + v) * 3;
-        if (f > 0) kp_unit_diff(x, x - (size_t)V * 3, gt, dv);
-        if (f < F - 1) kp_unit_diff(x, x + (size_t)V * 3, gt, dv);   // -(x1 - x) / |x1 - x| = (x - x1) / |x - x1|
-        for (int m = 0; m < IA_KP_N_VERTEX; m++)
-          if (skv[m] == v) { dv[0] += sdpt[fi][m][0]; dv[1] += sdpt[fi][m][1]; dv[2] += sdpt[fi][m][2]; }
+        if (GIVEN) {
+          dv[0] = x[0]; dv[1] = x[1]; dv[2] = x[2];
+        } else {
+          if (f > 0) kp_unit_diff(x, x - (size_t)V * 3, gt, dv);
+          if (f < F - 1) kp_unit_diff(x, x + (size_t)V * 3, gt, dv);   // -(x1 - x) / |x1 - x| = (x - x1) / |x - x1|
+          for (int m = 0; m < IA_KP_N_VERTEX; m++)
+            if (skv[m] == v) { dv[0] += sdpt[fi][m][0]; dv[1] += sdpt[fi][m][1]; dv[2] += sdpt[fi][m][2]; }
+        }
         float T[12];
         kp_blend(wt, sA[fi], T);
         for (int b = 0; b < 3; b++) {
@@ -495,7 +506,40 @@ extern "C" int ia_kp_loss_bwd(const ia_smpl_body *body, const float *betas, cons
   hipLaunchKernelGGL(k_kp_point_grad, dim3(ia_div_up((long)F * IA_KP_N_POINTS, KP_THREADS)), dim3(KP_THREADS), 0, s, w, verts, transl,
                      kp_vertex, B.V, F, proj, keypoints, threshold);
   IA_LAUNCH_CHECK("k_kp_point_grad");
-  hipLaunchKernelGGL(k_kp_vertex_bwd, dim3((unsigned)((long)n_vb * ia_div_up(F, KP_FT))), dim3(KP_THREADS), 0, s, B, betas, F, n_vb, w, verts, kp_vertex);
+  hipLaunchKernelGGL(k_kp_vertex_bwd<false>, dim3((unsigned)((long)n_vb * ia_div_up(F, KP_FT))), dim3(KP_THREADS), 0, s, B, betas, F, n_vb, w, verts, kp_vertex);
+  IA_LAUNCH_CHECK("k_kp_vertex_bwd");
+  hipLaunchKernelGGL(k_kp_reduce_v, dim3(ia_div_up((long)F * KP_NOUT, KP_THREADS)), dim3(KP_THREADS), 0, s, w, F, n_vb);
+  IA_LAUNCH_CHECK("k_kp_reduce_v");
+  hipLaunchKernelGGL(k_kp_chain_bwd, dim3(F), dim3(64), 0, s, B, betas, pose, w, d_pose, d_transl);
+  IA_LAUNCH_CHECK("k_kp_chain_bwd");
+  if (d_betas) {
+    hipLaunchKernelGGL(k_kp_reduce_f, dim3(1), dim3(64), 0, s, w, F, d_betas);
+    IA_LAUNCH_CHECK("k_kp_reduce_f");
+  }
+  return IA_OK;
+}
+
+// ---- the same backward for a vertex cotangent of the caller's (include/instantavatar_hip_silhouette.h) ---------------------------
+extern "C" size_t ia_sil_body_workspace_bytes(int n_frames, int n_verts) { return ia_kp_workspace_bytes(n_frames, n_verts); }
+
+extern "C" int ia_sil_body_bwd(const ia_smpl_body *body, const float *betas, const float *pose, const float *transl, int n_frames,
+                               const float *d_verts, float *d_betas, float *d_pose, float *d_transl, void *ws, size_t ws_bytes, void *stream) {
+  KpBodyDev B;
+  IA_CHECK_ARG(kp_make_body(body, &B) == 0, "ia_sil_body_bwd: incomplete body model");
+  IA_CHECK_ARG(n_frames >= 1, "ia_sil_body_bwd: n_frames = %d < 1", n_frames);
+  IA_CHECK_ARG(B.V >= 1, "ia_sil_body_bwd: body with n_verts = %d < 1", B.V);
+  IA_CHECK_ARG(kp_sizes_ok(n_frames, B.V), "ia_sil_body_bwd: n_frames * n_verts * 3 = %lld does not fit 31 bits", (long long)n_frames * B.V * 3);
+  IA_CHECK_ARG(betas && pose && transl && d_verts && ws, "ia_sil_body_bwd: null pointer");
+  IA_CHECK_ARG(ws_bytes >= ia_kp_workspace_bytes(n_frames, B.V), "ia_sil_body_bwd: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int F = n_frames, n_vb = ia_div_up(B.V, KP_THREADS);
+  KpWs w = kp_carve(ws, F, B.V);
+  hipLaunchKernelGGL(k_kp_chain_fwd, dim3(F), dim3(64), 0, s, B, betas, pose, w);
+  IA_LAUNCH_CHECK("k_kp_chain_fwd");
+  ia_zero_fill(w.dpoint, (size_t)F * IA_KP_N_POINTS * 3 * sizeof(float), s);   // no cotangent of the joints themselves
+  IA_LAUNCH_CHECK("k_zero_words");
+  hipLaunchKernelGGL(k_kp_vertex_bwd<true>, dim3((unsigned)((long)n_vb * ia_div_up(F, KP_FT))), dim3(KP_THREADS), 0, s, B, betas, F, n_vb, w, d_verts,
+                     (const int32_t *)nullptr);
   IA_LAUNCH_CHECK("k_kp_vertex_bwd");
   hipLaunchKernelGGL(k_kp_reduce_v, dim3(ia_div_up((long)F * KP_NOUT, KP_THREADS)), dim3(KP_THREADS), 0, s, w, F, n_vb);
   IA_LAUNCH_CHECK("k_kp_reduce_v");

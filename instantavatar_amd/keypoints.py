@@ -10,7 +10,7 @@ keypoint stage): the loss over all frames and its gradient are the HIP kernels o
 
 betas [10], pose [F,72] (global_orient then body_pose, axis-angle), transl [F,3]; proj [3,4] = intrinsic @ extrinsic[:3];
 keypoints [F,25,3] (x, y, confidence; BODY_25 order).  There is no CPU path.  The `--silhouette` stage of the reference (LBFGS per
-frame through a soft rasteriser; commented out in its own pipeline) is not implemented.
+frame through a soft rasteriser) is instantavatar_amd/silhouette.py.
 """
 import numpy as np
 import torch

@@ -173,6 +173,69 @@ def make_body(seed=42, blendshapes=False):
     )
 
 
+def make_mesh_body(sides=8, rings=5, seed=42):
+    """A synthetic SMPL-like body WITH triangles: the dict keys of `make_body` plus "f" [nf,3] int32 (what SMPL.faces_tensor reads).
+    One closed tube per capsule of `_segments(_JOINTS)`: `rings` regular `sides`-gons around the bone from its first joint to its
+    last, at the capsule's radius and with a seeded starting angle, and one cap vertex on the axis at either end -- 28 (rings sides
+    + 2) vertices and 28 * 2 sides rings faces, wound outwards.  The tubes overlap (a silhouette is a union).  Weights by
+    `make_body`'s rule (inverse 4th power of the distance to the 4 nearest bones); a J_regressor row averages the ring centred on
+    its joint, so J_regressor @ v_template == the joints; zero shape and pose directions.  sides = 16, rings = 15 is about SMPL's
+    size (6 776 vertices, 13 440 faces)."""
+    if sides < 3 or rings < 2:
+        raise ValueError("make_mesh_body: sides >= 3 and rings >= 2, got %d and %d" % (sides, rings))
+    rng = np.random.RandomState(seed)
+    J = _JOINTS.copy()
+    segs = _segments(J)
+    verts, faces, ring_of = [], [], {}
+    for si, (a, b, r, _) in enumerate(segs):
+        u, w = _frame(b - a)
+        ax = np.cross(u, w)                     # the bone's direction: (u, w, ax) is right-handed
+        ax = ax if ax @ (b - a) > 0 else -ax
+        phi0 = rng.uniform(0, 2 * np.pi)
+        base = len(verts)
+        for i in range(rings):
+            c = a + (b - a) * (i / (rings - 1))
+            for k in range(sides):
+                ang = phi0 + 2 * np.pi * k / sides
+                verts.append(c + r * (np.cos(ang) * u + np.sin(ang) * np.cross(ax, u)))
+        cap0, cap1 = len(verts), len(verts) + 1
+        verts.extend([a, b])
+        for k in range(sides):
+            k1 = (k + 1) % sides
+            for i in range(rings - 1):
+                p, q = base + i * sides, base + (i + 1) * sides
+                faces.extend([(p + k, p + k1, q + k1), (p + k, q + k1, q + k)])
+            faces.extend([(cap0, base + k1, base + k), (cap1, base + (rings - 1) * sides + k, base + (rings - 1) * sides + k1)])
+        if si < 23:                             # segment si ends at joint si + 1; joint 0 starts segment 0
+            ring_of[si + 1] = base + (rings - 1) * sides
+            if si == 0:
+                ring_of[0] = base
+    verts = np.asarray(verts)
+    V = len(verts)
+    dist = np.full((V, 24), 1e9)
+    for a, b, r, ctrl in segs:
+        dist[:, ctrl] = np.minimum(dist[:, ctrl], _seg_dist(verts, a, b))
+    wgt = 1.0 / (dist + 0.02) ** 4
+    order = np.argsort(-wgt, axis=1)
+    mask = np.zeros_like(wgt)
+    np.put_along_axis(mask, order[:, :4], 1.0, axis=1)
+    wgt = wgt * mask
+    wgt /= wgt.sum(1, keepdims=True)
+    Jreg = np.zeros((24, V))
+    for j in range(24):
+        Jreg[j, ring_of[j]:ring_of[j] + sides] = 1.0 / sides
+    return dict(
+        v_template=verts.astype(np.float32),
+        shapedirs=np.zeros((V, 3, 10), np.float32),
+        posedirs=np.zeros((207, V * 3), np.float32),
+        J_regressor=Jreg.astype(np.float32),
+        parents=SMPL_PARENTS.copy(),
+        lbs_weights=wgt.astype(np.float32),
+        joints_template=J.astype(np.float32),
+        f=np.asarray(faces, np.int32),
+    )
+
+
 def cano_pose(name="A_pose"):
     """snarf_deformer.py:6-18 (get_predefined_rest_pose)."""
     p = np.zeros(69, np.float32)
