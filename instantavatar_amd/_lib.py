@@ -74,6 +74,9 @@ KEYPOINTS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar
 # and the soft-silhouette entry points (csrc/ia_silhouette.hip): `silhouette_declarations`
 SILHOUETTE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_silhouette.h")
 
+# and the mask-cleaning entry points (csrc/ia_masks.hip): `masks_declarations`
+MASKS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_masks.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -246,6 +249,23 @@ def silhouette_declarations():
     return _silhouette_decls
 
 
+_masks_decls = None
+
+
+def masks_declarations():
+    """parse_header of include/instantavatar_hip_masks.h, read once: an eighth table, bound in `lib()` and reachable through
+    `call` like the other seven; its names are disjoint from theirs."""
+    global _masks_decls
+    if _masks_decls is None:
+        d = _parse_file(MASKS_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_masks.h declares %s, which another header declares already" % ", ".join(both))
+        _masks_decls = d
+    return _masks_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -285,7 +305,7 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, d in list(declarations().items()) + list(io_declarations().items()) + list(normals_declarations().items()) \
                 + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()) \
-                + list(silhouette_declarations().items()):
+                + list(silhouette_declarations().items()) + list(masks_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -373,7 +393,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

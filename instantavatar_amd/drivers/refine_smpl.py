@@ -75,7 +75,8 @@ def read_masks(root, n_frames, pose_path, downscale, device):
     from ..datasets.sequence_dir import resize_rule
     mdir = os.path.join(os.fspath(root), "masks")
     if not os.path.isdir(mdir):
-        raise _error(mdir, "is missing: no masks for --silhouette (one image per frame)")
+        raise _error(mdir, "is missing: no masks for --silhouette (one image per frame; `python -m instantavatar_amd.drivers.clean_masks "
+                             "--data DIR` writes them from the raw masks in DIR/masks_sam)")
     files = sorted(glob.glob(os.path.join(mdir, "*")))
     if len(files) != n_frames:
         raise _error(mdir, "%d mask%s but %d rows of poses in %s" % (len(files), "" if len(files) == 1 else "s", n_frames, pose_path))
@@ -172,7 +173,8 @@ def main(argv=None):
                 raise _error("the body model", "has no faces: --silhouette needs triangles (an SMPL file with `f`, or --synthetic-mesh-body)")
             mdir = os.path.join(args.data, "masks")
             if not os.path.isdir(mdir):
-                raise _error(mdir, "is missing: no masks for --silhouette (one image per frame)")
+                raise _error(mdir, "is missing: no masks for --silhouette (one image per frame; `python -m instantavatar_amd.drivers.clean_masks "
+                             "--data DIR` writes them from the raw masks in DIR/masks_sam)")
         except SequenceError as e:
             raise SystemExit("--data %s: %s" % (args.data, e))
     kw = {}
