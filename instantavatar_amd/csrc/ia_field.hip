@@ -410,16 +410,36 @@ __device__ __forceinline__ void save_rows(uint16_t *__restrict__ dst, const floa
 #ifndef IA_FIELD_THREADS
 #define IA_FIELD_THREADS 768
 #endif
-#define IA_FIELD_WAVES (IA_FIELD_THREADS / 64)
+// The planes-route inference instantiations (SAVE = false, PLANES = true: the render MLP behind k_encode_xcd) run as
+// workgroups of one wave per SIMD, IA_FIELD_PLANES_WG_PER_CU of them per CU: the same 12 waves per CU and the same register
+// budget per wave (IA_FIELD_PLANES_WAVES_PER_SIMD) as one 768-thread workgroup, but a workgroup needs 160 VGPRs per SIMD and
+// 22 KB of LDS instead of 480 and a drained CU, so it starts beside three resident k_search workgroups.
+// Training and the fused routes (up to 72 KB of staged table per workgroup) keep IA_FIELD_THREADS.
+#ifndef IA_FIELD_PLANES_THREADS
+#define IA_FIELD_PLANES_THREADS 256
+#endif
+#ifndef IA_FIELD_PLANES_WG_PER_CU
+#define IA_FIELD_PLANES_WG_PER_CU 3
+#endif
+#ifndef IA_FIELD_PLANES_WAVES_PER_SIMD
+#define IA_FIELD_PLANES_WAVES_PER_SIMD 3
+#endif
+__host__ __device__ constexpr int field_threads(bool save, bool planes) {
+  return (planes && !save) ? IA_FIELD_PLANES_THREADS : IA_FIELD_THREADS;
+}
+__host__ __device__ constexpr int field_waves_per_simd(bool save, bool planes) {
+  return (planes && !save) ? IA_FIELD_PLANES_WAVES_PER_SIMD : IA_FIELD_THREADS / 256;
+}
 
 template <int L, bool SAVE, int NLDS, int NDENSE, bool PLANES = false>
-__global__ __launch_bounds__(IA_FIELD_THREADS) void k_field(const float *__restrict__ x, int V,
+__global__ __launch_bounds__(field_threads(SAVE, PLANES), field_waves_per_simd(SAVE, PLANES)) void k_field(const float *__restrict__ x, int V,
                                                const int32_t *__restrict__ n_dev, FieldDev F,
                                                float *__restrict__ rgb, float *__restrict__ sigma,
                                                unsigned long long *prof, uint16_t *__restrict__ acts,
                                                int lds_entries, const uint32_t *__restrict__ planes = nullptr,
                                                size_t plane_stride = 0) {
   constexpr int ACT_STRIDE = 2 * L + 64 + 16 + 64 + 64;
+  constexpr int THREADS = field_threads(SAVE, PLANES), WAVES = THREADS / 64;
   extern __shared__ __attribute__((aligned(16))) char s_dyn[];
   half8 (*s_frag)[64] = reinterpret_cast<half8 (*)[64]>(s_dyn);
   const uint32_t *s_tab = reinterpret_cast<const uint32_t *>(s_dyn + N_FRAG * 64 * 16);
@@ -427,9 +447,9 @@ __global__ __launch_bounds__(IA_FIELD_THREADS) void k_field(const float *__restr
   if (prof && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(prof, (unsigned long long)V);
   const int n_tiles = (V + 63) >> 6;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // tiles go round-robin over workgroups first (one workgroup per CU), then over its waves:
-  // a small launch still spreads over all 256 CUs
-  const int tile_stride = gridDim.x * IA_FIELD_WAVES;
+  // tiles go round-robin over workgroups first (consecutive workgroups land on different CUs), then over a
+  // workgroup's waves: a small launch still spreads over all 256 CUs
+  const int tile_stride = gridDim.x * WAVES;
   int tile = blockIdx.x + wave * gridDim.x;
   if ((int)blockIdx.x >= n_tiles) return;  // whole workgroup idle
   // stage the coarsest dense levels (entries [0, lds_entries) of the table) in LDS
@@ -437,16 +457,16 @@ __global__ __launch_bounds__(IA_FIELD_THREADS) void k_field(const float *__restr
     uint32_t *dst = reinterpret_cast<uint32_t *>(s_dyn + N_FRAG * 64 * 16);
     const uint4 *src4 = reinterpret_cast<const uint4 *>(F.table);
     uint4 *dst4 = reinterpret_cast<uint4 *>(dst);
-    for (int e = threadIdx.x; e < lds_entries / 4; e += IA_FIELD_THREADS) dst4[e] = src4[e];
+    for (int e = threadIdx.x; e < lds_entries / 4; e += THREADS) dst4[e] = src4[e];
   }
   // A fragments: copy the prebuilt image (ia_field_prepare) or build it here
   if (F.frags) {
     const uint4 *src = reinterpret_cast<const uint4 *>(F.frags);
     uint4 *dst = reinterpret_cast<uint4 *>(&s_frag[0][0]);
 #pragma unroll
-    for (int e = threadIdx.x; e < N_FRAG * 64; e += IA_FIELD_THREADS) dst[e] = src[e];
+    for (int e = threadIdx.x; e < N_FRAG * 64; e += THREADS) dst[e] = src[e];
   } else {
-    for (int e = threadIdx.x; e < N_FRAG * 64 * 8; e += IA_FIELD_THREADS) {
+    for (int e = threadIdx.x; e < N_FRAG * 64 * 8; e += THREADS) {
       const int f = e >> 9, l = (e >> 3) & 63, p = e & 7;
       reinterpret_cast<_Float16 *>(&s_frag[f][l])[p] = frag_value<L>(F, f, l & 31, l >> 5, p);
     }
@@ -634,7 +654,7 @@ int ia_launch_field(const float *x, int V, const int32_t *n_dev, const FieldDev 
   }
   unsigned long long *prof = ia_prof_units(IA_PROF_FIELD);
   ia_prof_begin(IA_PROF_FIELD, s);
-  const dim3 g(blocks), b(IA_FIELD_THREADS);
+  dim3 g(blocks), b(IA_FIELD_THREADS);
   const int L16 = F.lv.n_levels == 16;
   const uint32_t *planes = nullptr;
   const size_t stride = F.enc_ws_samples;
@@ -645,6 +665,11 @@ int ia_launch_field(const float *x, int V, const int32_t *n_dev, const FieldDev 
     int rc = ia_launch_encode_xcd(x, V, n_dev, F, F.enc_ws, stride, s);
     if (rc != IA_OK) return rc;
     planes = F.enc_ws;
+    if (!acts) {  // one-wave-per-SIMD workgroups, IA_FIELD_PLANES_WG_PER_CU per CU (a workgroup without a tile returns at once)
+      const int cap = 256 * IA_FIELD_PLANES_WG_PER_CU;
+      g = dim3(tiles < cap ? tiles : cap);
+      b = dim3(field_threads(false, true));
+    }
     if (acts) { if (L16) IA_LF(16, true, 0, 4, true); else IA_LF(8, true, 0, 4, true); }
     else { if (L16) IA_LF(16, false, 0, 4, true); else IA_LF(8, false, 0, 4, true); }
   } else if (pattern) {
