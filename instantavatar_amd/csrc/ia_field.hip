@@ -236,13 +236,30 @@ __device__ __forceinline__ void encode_all(const FieldDev &F, const uint32_t *__
 // per (y, z) pair; one lane in four adds a predicated 4-byte load (hashed_quad_loads).
 // ---------------------------------------------------------------------------
 #ifndef IA_ENC_S
-#define IA_ENC_S 3  // samples per thread (table gathers in flight per lane: 4-5 per sample)
+#define IA_ENC_S 3  // samples per thread (table gathers in flight per lane: 4-5 per sample): training forward, ia_hashgrid_fwd_planes
+#endif
+// Samples per thread of the inference planes route (ia_launch_field without an activation record on the sharded path: the
+// render loop, the occupancy probes, ia_deform_query).  The register footprint follows it -- 3: 124 VGPRs (128 allocated, 4
+// waves per SIMD), 2: 86 (88, 5), 1: 51 (56, 8) -- and with it when a workgroup gets onto a CU beside other frames'
+// k_search workgroups.  Measured (profiles/encode_coresidency_ab.txt): 2 is the fastest with three
+// frames in flight and with one; 1 pays more for the fewer gathers in flight per wave than the residency returns.
+// Per-sample arithmetic does not depend on the shape: features are bit-identical.
+#ifndef IA_ENC_S_RENDER
+#define IA_ENC_S_RENDER 2
+#endif
+#if IA_ENC_S < 1 || IA_ENC_S > 3 || IA_ENC_S_RENDER < 1 || IA_ENC_S_RENDER > 3
+#error "IA_ENC_S and IA_ENC_S_RENDER must be 1, 2 or 3"
 #endif
 #define IA_ENC_THREADS 256
-#define IA_ENC_TILE (IA_ENC_S * IA_ENC_THREADS)
-#ifndef IA_ENC_MAX_WG_PER_XCD
-#define IA_ENC_MAX_WG_PER_XCD 256  // 32 CUs x 8 resident workgroups
-#endif
+// Register budget of a shape: VGPRs allocated per wave (the compiler's count rounded up to the granule of 8) and the waves
+// per SIMD that leaves of the 512-entry file (at most 8).  The budget is pinned with the second __launch_bounds__ argument;
+// a workgroup is one wave per SIMD, so an XCD (32 CUs) holds 32 x enc_waves_per_simd(S) workgroups: the grid cap.
+__host__ __device__ constexpr int enc_vgprs(int S) { return S == 1 ? 56 : S == 2 ? 88 : 128; }
+__host__ __device__ constexpr int enc_waves_per_simd(int S) { return 512 / enc_vgprs(S) < 8 ? 512 / enc_vgprs(S) : 8; }
+__host__ __device__ constexpr int enc_max_wg_per_xcd(int S) { return 32 * enc_waves_per_simd(S); }
+// second __launch_bounds__ argument.  3 samples per thread stay unpinned (0): the budget of 128 is what the compiler takes
+// by itself, and pinning it renames registers in code that is otherwise instruction for instruction the same.
+__host__ __device__ constexpr int enc_pinned_waves(int S) { return S == 3 ? 0 : enc_waves_per_simd(S); }
 
 // Round 6: the aligned 16-byte GROUP of four table entries around corner x instead of its aligned pair.  With tcnn's
 // hash the x-neighbour of a corner is entry (x + 1) ^ h: inside the same aligned pair when x is even, inside the same aligned group
@@ -300,13 +317,14 @@ __device__ __forceinline__ uint32_t hashed_quad_reduce(const float w[3], const u
   return o.u;
 }
 
-template <int L>
-__global__ __launch_bounds__(IA_ENC_THREADS) void k_encode_xcd(const float *__restrict__ x, int V,
+template <int L, int S>
+__global__ __launch_bounds__(IA_ENC_THREADS, enc_pinned_waves(S)) void k_encode_xcd(const float *__restrict__ x, int V,
                                                                 const int32_t *__restrict__ n_dev, FieldDev F,
                                                                 uint32_t *__restrict__ planes, size_t stride) {
   constexpr int ND = 4, NH = L - ND;  // tcnn default pattern (checked by the host)
+  constexpr int TILE = S * IA_ENC_THREADS;
   if (n_dev) V = min(V, *n_dev);
-  const int n_tiles = (V + IA_ENC_TILE - 1) / IA_ENC_TILE;
+  const int n_tiles = (V + TILE - 1) / TILE;
   // Work items of an XCD: (16 levels) first EVERY tile of hashed level 4 + xcd, then tiles of the second level group -- hashed level
   // 12 + (xcd & 3) together with dense level (xcd & 3) -- which XCD k shares with XCD k + 4: of every four tiles XCD k takes the
   // first `spl`, XCD k + 4 the rest.  spl = F.enc_split is the caller's hint (ia_field.enc_split): on spatially coherent samples
@@ -327,10 +345,10 @@ __global__ __launch_bounds__(IA_ENC_THREADS) void k_encode_xcd(const float *__re
       tile = q * 4 + (xcd < 4 ? r : spl + r); lev_h = (NH > 4 ? ND + 8 : ND) + (xcd & 3); lev_d = xcd & 3;
     }
     if (tile >= n_tiles) continue;
-    const int base = tile * IA_ENC_TILE + threadIdx.x;
-    float xn[IA_ENC_S][3];
+    const int base = tile * TILE + threadIdx.x;
+    float xn[S][3];
 #pragma unroll
-    for (int k = 0; k < IA_ENC_S; k++) {
+    for (int k = 0; k < S; k++) {
       const int i = base + k * IA_ENC_THREADS;
       xn[k][0] = xn[k][1] = xn[k][2] = 0.f;
       if (i < V) normalise(F, x, (size_t)i, xn[k]);
@@ -338,13 +356,13 @@ __global__ __launch_bounds__(IA_ENC_THREADS) void k_encode_xcd(const float *__re
     {
       const uint32_t *tab = F.table + F.hash_base + (uint32_t)(lev_h - ND) * F.hash_size;
       const float scale = F.lv.scale[lev_h];
-      float w[IA_ENC_S][3];
+      float w[S][3];
       uint32_t *out = planes + (size_t)lev_h * stride;
-      uint32_t qx[IA_ENC_S][4], qy[IA_ENC_S][4], qz[IA_ENC_S][4], qw[IA_ENC_S][4], ext[IA_ENC_S][4], meta[IA_ENC_S];
+      uint32_t qx[S][4], qy[S][4], qz[S][4], qw[S][4], ext[S][4], meta[S];
 #pragma unroll
-      for (int k = 0; k < IA_ENC_S; k++) hashed_quad_loads(tab, scale, F.hash_size - 1, xn[k], w[k], qx[k], qy[k], qz[k], qw[k], ext[k], meta[k]);
+      for (int k = 0; k < S; k++) hashed_quad_loads(tab, scale, F.hash_size - 1, xn[k], w[k], qx[k], qy[k], qz[k], qw[k], ext[k], meta[k]);
 #pragma unroll
-      for (int k = 0; k < IA_ENC_S; k++) {
+      for (int k = 0; k < S; k++) {
         const int i = base + k * IA_ENC_THREADS;
         const uint32_t f = hashed_quad_reduce(w[k], qx[k], qy[k], qz[k], qw[k], ext[k], meta[k]);
         if (i < V) out[i] = f;
@@ -354,13 +372,13 @@ __global__ __launch_bounds__(IA_ENC_THREADS) void k_encode_xcd(const float *__re
       const uint32_t *tab = F.table + F.lv.offset[lev_d];
       const float scale = F.lv.scale[lev_d];
       const uint32_t res = F.lv.res[lev_d], size = F.lv.size[lev_d];
-      float w[IA_ENC_S][3];
-      uint32_t lo[IA_ENC_S][4], hi[IA_ENC_S][4], ext[IA_ENC_S][4], meta[IA_ENC_S];
+      float w[S][3];
+      uint32_t lo[S][4], hi[S][4], ext[S][4], meta[S];
 #pragma unroll
-      for (int k = 0; k < IA_ENC_S; k++) level_loads<1>(tab, scale, res, size, xn[k], w[k], lo[k], hi[k], ext[k], meta[k]);
+      for (int k = 0; k < S; k++) level_loads<1>(tab, scale, res, size, xn[k], w[k], lo[k], hi[k], ext[k], meta[k]);
       uint32_t *out = planes + (size_t)lev_d * stride;
 #pragma unroll
-      for (int k = 0; k < IA_ENC_S; k++) {
+      for (int k = 0; k < S; k++) {
         const int i = base + k * IA_ENC_THREADS;
         const uint32_t f = level_reduce<1>(w[k], lo[k], hi[k], ext[k], meta[k]);
         if (i < V) out[i] = f;
@@ -374,19 +392,29 @@ static inline bool ia_field_shardable(const FieldDev &F) {
   return (L == 8 || L == 16) && F.n_dense == 4 && F.hash_size != 0 && (F.hash_size & (F.hash_size - 1)) == 0;
 }
 
-static int ia_launch_encode_xcd(const float *x, int V, const int32_t *n_dev, const FieldDev &F, uint32_t *planes,
-                                size_t stride, hipStream_t s) {
-  const int tiles = (V + IA_ENC_TILE - 1) / IA_ENC_TILE;
+template <int S>
+static int ia_launch_encode_xcd_shape(const float *x, int V, const int32_t *n_dev, const FieldDev &F, uint32_t *planes,
+                                      size_t stride, hipStream_t s) {
+  constexpr int TILE = S * IA_ENC_THREADS;
+  const int tiles = (V + TILE - 1) / TILE;
   const int L = F.lv.n_levels;
   const int spl = L == 16 ? F.enc_split : 2, mx = spl > 4 - spl ? spl : 4 - spl;
   int per_xcd = (L == 16 ? tiles : 0) + ((tiles + 3) / 4) * mx;
-  if (per_xcd > IA_ENC_MAX_WG_PER_XCD) per_xcd = IA_ENC_MAX_WG_PER_XCD;  // workgroups loop over their XCD's items
+  if (per_xcd > enc_max_wg_per_xcd(S)) per_xcd = enc_max_wg_per_xcd(S);  // workgroups loop over their XCD's items
   if (L == 16)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_encode_xcd<16>), dim3(8 * per_xcd), dim3(IA_ENC_THREADS), 0, s, x, V, n_dev, F, planes, stride);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_encode_xcd<16, S>), dim3(8 * per_xcd), dim3(IA_ENC_THREADS), 0, s, x, V, n_dev, F, planes, stride);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_encode_xcd<8>), dim3(8 * per_xcd), dim3(IA_ENC_THREADS), 0, s, x, V, n_dev, F, planes, stride);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_encode_xcd<8, S>), dim3(8 * per_xcd), dim3(IA_ENC_THREADS), 0, s, x, V, n_dev, F, planes, stride);
   IA_LAUNCH_CHECK("k_encode_xcd");
   return IA_OK;
+}
+
+// `shape`: samples per thread, IA_ENC_S_RENDER (inference planes route) or IA_ENC_S (training forward, stand-alone planes)
+static int ia_launch_encode_xcd(const float *x, int V, const int32_t *n_dev, const FieldDev &F, uint32_t *planes,
+                                size_t stride, hipStream_t s, int shape) {
+  if (shape == IA_ENC_S_RENDER) return ia_launch_encode_xcd_shape<IA_ENC_S_RENDER>(x, V, n_dev, F, planes, stride, s);
+  if (shape == IA_ENC_S) return ia_launch_encode_xcd_shape<IA_ENC_S>(x, V, n_dev, F, planes, stride, s);
+  return ia_set_error(IA_ERR_ARG, "ia_launch_encode_xcd: no instantiation for %d samples per thread", shape);
 }
 
 // activation record written in training mode (fp16, IA_ACT_STRIDE halves per sample):
@@ -662,7 +690,7 @@ int ia_launch_field(const float *x, int V, const int32_t *n_dev, const FieldDev 
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_field<LV, SV, NL, ND, PL>), g, b, shmem, s, x, V, n_dev, F, rgb, sigma, prof, acts, \
                      pattern ? lds_entries : 0, planes, stride)
   if (sharded) {
-    int rc = ia_launch_encode_xcd(x, V, n_dev, F, F.enc_ws, stride, s);
+    int rc = ia_launch_encode_xcd(x, V, n_dev, F, F.enc_ws, stride, s, acts ? IA_ENC_S : IA_ENC_S_RENDER);
     if (rc != IA_OK) return rc;
     planes = F.enc_ws;
     if (!acts) {  // one-wave-per-SIMD workgroups, IA_FIELD_PLANES_WG_PER_CU per CU (a workgroup without a tile returns at once)
@@ -1309,7 +1337,7 @@ extern "C" int ia_hashgrid_fwd_planes(const float *x, int V, const ia_field *fie
   int rc = ia_make_field_dev(field, &F);
   IA_CHECK_ARG(rc == 0, "ia_hashgrid_fwd_planes: bad field descriptor (%d)", rc);
   IA_CHECK_ARG(ia_field_shardable(F), "ia_hashgrid_fwd_planes: level table is not 4 dense + 4/12 uniform hashed levels");
-  return ia_launch_encode_xcd(x, V, nullptr, F, planes, stride, (hipStream_t)stream);
+  return ia_launch_encode_xcd(x, V, nullptr, F, planes, stride, (hipStream_t)stream, IA_ENC_S);
 }
 
 extern "C" int ia_hash_desc_init(ia_hash_desc *o, int n_levels, int log2_hashmap_size, int base_resolution,

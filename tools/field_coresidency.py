@@ -6,6 +6,10 @@ the ones that wait for CUs.
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -o r -- python bench.py --steps 200 --warmup 20 [--in-flight 1]
     python tools/field_coresidency.py DIR/.../r_kernel_trace.csv [frames]      (the last `frames` frames, default 150)
+
+Another kernel is looked at the same way with `--kernel NAME [--after PREDECESSOR]`: every launch whose name contains NAME, the gap
+behind the last launch of the same stream whose name contains PREDECESSOR.  The hash-grid encoder behind its stream's search:
+    python tools/field_coresidency.py DIR/.../r_kernel_trace.csv [frames] --kernel k_encode_xcd --after k_search
 """
 import bisect
 import collections
@@ -27,7 +31,9 @@ def pct(v, q):
     return v[min(len(v) - 1, int(q * len(v)))]
 
 
-def main(path, frames=150):
+def main(path, frames=150, kernel=None, after="k_encode_xcd"):
+    match = (lambda n: kernel in n) if kernel else FIELD.search
+    label = kernel if kernel else "k_field<L,false,0,4,true>"
     rows = list(csv.DictReader(open(path)))
     key = "Stream_Id" if rows and "Stream_Id" in rows[0] and len({r["Stream_Id"] for r in rows}) > 1 else "Queue_Id"
     ks = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r[key],
@@ -47,9 +53,9 @@ def main(path, frames=150):
     dur, gap, cover = [], [], collections.defaultdict(float)
     search_cov, alone, shape = [], 0, collections.Counter()
     for i, (s, e, name, q, wg, grid, vgpr, lds) in enumerate(ks):
-        if "k_encode_xcd" in name:
-            last_enc[q] = e
-        if not FIELD.search(name):
+        if not match(name):
+            if after in name:
+                last_enc[q] = e
             continue
         shape[(wg, vgpr, lds)] += 1
         dur.append((e - s) / 1e3)
@@ -66,15 +72,15 @@ def main(path, frames=150):
         alone += not ov
     n = len(dur)
     if not n:
-        print("no k_field<L, false, 0, 4, true> launch found")
+        print("no %s launch found" % (kernel or "k_field<L, false, 0, 4, true>"))
         return
-    print("k_field<L,false,0,4,true>: %d launches (%.1f per frame); (threads per workgroup, VGPRs, LDS bytes): %s"
-          % (n, n / max(n_frames, 1), sorted(shape.items())))
+    print("%s: %d launches (%.1f per frame); (threads per workgroup, VGPRs, LDS bytes): %s"
+          % (label, n, n / max(n_frames, 1), sorted(shape.items())))
     print("  duration us   mean %.1f  median %.1f  p90 %.1f  max %.1f   sum per frame %.1f us"
           % (statistics.mean(dur), statistics.median(dur), pct(dur, 0.9), max(dur), sum(dur) / max(n_frames, 1)))
     if gap:
-        print("  gap after the stream's k_encode_xcd us   mean %.1f  median %.1f  p90 %.1f  max %.1f   sum per frame %.1f us"
-              % (statistics.mean(gap), statistics.median(gap), pct(gap, 0.9), max(gap), sum(gap) / max(n_frames, 1)))
+        print("  gap after the stream's %s us   mean %.1f  median %.1f  p90 %.1f  max %.1f   sum per frame %.1f us"
+              % (after, statistics.mean(gap), statistics.median(gap), pct(gap, 0.9), max(gap), sum(gap) / max(n_frames, 1)))
     print("  launches with no kernel of another stream running during them: %d (%.0f %%)" % (alone, 100.0 * alone / n))
     print("  k_search launches of other streams running during a launch (time-weighted mean count): %.2f" % statistics.mean(search_cov))
     print("  kernels of other streams during a launch, mean share of its interval covered (can exceed 1: several streams):")
@@ -83,4 +89,11 @@ def main(path, frames=150):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 150)
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("trace")
+    ap.add_argument("frames", nargs="?", type=int, default=150)
+    ap.add_argument("--kernel", default=None, help="substring of the kernel's name (default: the planes-route render MLP)")
+    ap.add_argument("--after", default="k_encode_xcd", help="substring of the same stream's predecessor, for the gap line")
+    a = ap.parse_args()
+    main(a.trace, a.frames, a.kernel, a.after)
