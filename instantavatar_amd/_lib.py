@@ -77,6 +77,9 @@ SILHOUETTE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavata
 # and the mask-cleaning entry points (csrc/ia_masks.hip): `masks_declarations`
 MASKS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_masks.h")
 
+# and the sequence-inspection entry points (csrc/ia_overlay.hip): `overlay_declarations`
+OVERLAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_overlay.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -266,6 +269,24 @@ def masks_declarations():
     return _masks_decls
 
 
+_overlay_decls = None
+
+
+def overlay_declarations():
+    """parse_header of include/instantavatar_hip_overlay.h, read once: a ninth table, bound in `lib()` and reachable through
+    `call` like the other eight; its names are disjoint from theirs."""
+    global _overlay_decls
+    if _overlay_decls is None:
+        d = _parse_file(OVERLAY_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
+                                | set(masks_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_overlay.h declares %s, which another header declares already" % ", ".join(both))
+        _overlay_decls = d
+    return _overlay_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -305,7 +326,7 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, d in list(declarations().items()) + list(io_declarations().items()) + list(normals_declarations().items()) \
                 + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()) \
-                + list(silhouette_declarations().items()) + list(masks_declarations().items()):
+                + list(silhouette_declarations().items()) + list(masks_declarations().items()) + list(overlay_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -393,7 +414,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:
