@@ -80,6 +80,9 @@ MASKS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip
 # and the sequence-inspection entry points (csrc/ia_overlay.hip): `overlay_declarations`
 OVERLAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_overlay.h")
 
+# and the mesh-processing entry points (csrc/ia_meshops.hip): `meshops_declarations`
+MESHOPS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_meshops.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -287,6 +290,24 @@ def overlay_declarations():
     return _overlay_decls
 
 
+_meshops_decls = None
+
+
+def meshops_declarations():
+    """parse_header of include/instantavatar_hip_meshops.h, read once: a tenth table, bound in `lib()` and reachable through
+    `call` like the other nine; its names are disjoint from theirs."""
+    global _meshops_decls
+    if _meshops_decls is None:
+        d = _parse_file(MESHOPS_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
+                                | set(masks_declarations()) | set(overlay_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_meshops.h declares %s, which another header declares already" % ", ".join(both))
+        _meshops_decls = d
+    return _meshops_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -326,7 +347,8 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, d in list(declarations().items()) + list(io_declarations().items()) + list(normals_declarations().items()) \
                 + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()) \
-                + list(silhouette_declarations().items()) + list(masks_declarations().items()) + list(overlay_declarations().items()):
+                + list(silhouette_declarations().items()) + list(masks_declarations().items()) + list(overlay_declarations().items()) \
+                + list(meshops_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -414,7 +436,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

@@ -15,7 +15,12 @@ the canonical mesh.  Files: `canonical.<format>`, `posed_<i>.<format>`.
 centre, looking along +z at the centre with world +y up in the image, focal length SIZE pixels, at the distance at which the
 box's nearest face spans 90 % of the image (`raster.look_at_box`); with --poses, `posed_<i>.png` (vertex colours) and
 `posed_shaded_<i>.png` (lit from the camera) show every posed mesh under the animate driver's camera scaled to SIZE.  Alpha is
-the raster mask."""
+the raster mask.
+
+--smooth ITERS and --simplify K process the canonical mesh before anything is written ("mesh simplification"):
+first ITERS Taubin iterations, then vertex clustering with quadrics on a grid whose cell edge is K lattice spacings, a spacing
+being max(hi - lo) / (resolution - 1) of the field's box.  The processed mesh is the one that is written, posed and drawn.  One
+line reports `N -> M vertices, N -> M faces` and the wall time of each stage."""
 import argparse
 import os
 import sys
@@ -45,10 +50,16 @@ def main(argv=None):
     ap.add_argument("--keep", choices=("largest", "all"), default="largest", help="largest: only the connected component with the largest area")
     ap.add_argument("--format", choices=("ply", "obj"), default="ply")
     ap.add_argument("--render", type=int, default=0, metavar="SIZE", help="also write SIZE x SIZE pictures of the meshes (GPU rasteriser)")
+    ap.add_argument("--smooth", type=int, default=0, metavar="ITERS", help="Taubin iterations on the canonical mesh (0: none)")
+    ap.add_argument("--simplify", type=float, default=0.0, metavar="K", help="cluster the vertices on a grid of K >= 1 lattice spacings (0: no)")
     ap.add_argument("--out", default="meshes/out")
     args = ap.parse_args(argv)
     if not args.synthetic and not args.ckpt:
         ap.error("--ckpt is required unless --synthetic is given")
+    if args.smooth < 0:
+        ap.error("--smooth %d: the number of iterations cannot be negative" % args.smooth)
+    if args.simplify != 0 and not args.simplify >= 1:
+        ap.error("--simplify %g: the cell edge is given in lattice spacings and must be at least 1" % args.simplify)
     import torch
     device = torch.device("cuda:0")
     model, betas = animate.build_model(args, device)
@@ -57,9 +68,30 @@ def main(argv=None):
     write = lambda mesh, name: getattr(mesh, "to_" + args.format)(os.path.join(args.out, "%s.%s" % (name, args.format)))
     timings = {}
     mesh = model.extract_mesh(resolution=args.resolution, level=args.level, largest=args.keep == "largest", timings=timings)
+    extracted = mesh
+    if args.smooth or args.simplify:
+        from .. import mesh as mesh_mod
+        stages = []
+
+        def timed(name, fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            stages.append("%s %.3f s" % (name, time.perf_counter() - t0))
+            return out
+        if args.smooth:
+            mesh = timed("smooth", lambda: model.smooth_mesh(mesh, args.smooth))
+        if args.simplify:
+            lo, hi = mesh_mod.field_box(model.net_coarse)
+            cell = args.simplify * float((hi.astype(np.float64) - lo.astype(np.float64)).max()) / (args.resolution - 1)
+            mesh = timed("simplify", lambda: model.simplify_mesh(mesh, cell))
     write(mesh, "canonical")
     print("canonical mesh: %d vertices, %d faces at resolution %d, level %g (field %.3f s, count + emit %.3f s, component filter %.3f s)"
-          % (mesh.verts.shape[0], mesh.faces.shape[0], args.resolution, args.level, timings["field"], timings["isosurface"], timings["component"]))
+          % (extracted.verts.shape[0], extracted.faces.shape[0], args.resolution, args.level, timings["field"], timings["isosurface"], timings["component"]))
+    if mesh is not extracted:
+        print("processed mesh: %d -> %d vertices, %d -> %d faces (%s)"
+              % (extracted.verts.shape[0], mesh.verts.shape[0], extracted.faces.shape[0], mesh.faces.shape[0], ", ".join(stages)))
     if args.render:
         from PIL import Image
         from .. import mesh as mesh_mod, raster

@@ -1,7 +1,9 @@
 """Triangle meshes of the avatar: the isosurface of the canonical density field by marching tetrahedra on the GPU
 (csrc/ia_isosurface.hip, include/instantavatar_hip_mesh.h; definition in DESIGN.md section 4, "isosurface"), its largest
 connected component, per-vertex colours and normals from the field, forward skinning into a posed frame, and PLY / OBJ
-writers (numpy only).  `AvatarModel.extract_mesh` / `AvatarModel.pose_mesh` are the public entry points.
+writers (numpy only).  `AvatarModel.extract_mesh` / `AvatarModel.pose_mesh` are the public entry points.  `simplify`, `smooth` and
+`vertex_normals` process a mesh afterwards (csrc/ia_meshops.hip, include/instantavatar_hip_meshops.h; DESIGN.md section 4, "mesh
+simplification"): vertex clustering with quadrics, Taubin smoothing, normals from the faces.
 
 The level is OURS: the reference ships a marching-cubes helper it never calls, whose default level 0 is meant for signed
 distances; sigma = 10 is a density at which a 1 cm step is already ~10 % opaque.  It is a parameter."""
@@ -27,6 +29,14 @@ class Mesh:
         normal8, shaded8 [H,W,4] uint8, depth [H,W], mask [H,W] (and face_id) -- see `raster.render`."""
         from . import raster
         return raster.render(self, camera, light, cull)
+
+    def simplify(self, cell, box=None, reg=1e-3):
+        """`simplify(self, cell, box, reg)`: one vertex per occupied cell of edge `cell`"""
+        return simplify(self, cell, box, reg)
+
+    def smooth(self, iters=10, lam=0.5, mu=-0.53):
+        """`smooth(self, iters, lam, mu)`: Taubin smoothing of the positions"""
+        return smooth(self, iters, lam, mu)
 
     def _host(self):
         f = lambda t: t.detach().cpu().numpy()
@@ -200,3 +210,115 @@ def pose(deformer, mesh, batch):
         idx = torch.arange(nv, dtype=torch.int32, device=dev)
         _lib.call("ia_normals_from_gradient", verts, (-mesh.normals).contiguous(), idx, nv, None, vJ, grid, w2s, nv, normals)
     return Mesh(xd, mesh.faces, normals, mesh.colors)
+
+
+# ---- processing of a mesh: csrc/ia_meshops.hip --------------------------------------------------------------------------------------
+MAX_CLUSTER_CELLS = 1 << 27
+
+
+class Adjacency:
+    """the per-vertex face and neighbour lists of (verts, faces), built once on the device (ia_mesh_adjacency_build) and read by
+    `taubin` and `normals`; the lists depend on the faces and on which vertices are finite, not on the positions"""
+
+    def __init__(self, verts, faces):
+        _lib.require_cuda(verts, faces)
+        self.faces = faces.detach().to(torch.int32).contiguous()
+        self.nv, self.nf = int(verts.shape[0]), int(self.faces.shape[0])
+        self.nbytes = int(_lib.call("ia_mesh_adjacency_workspace_bytes", self.nv, self.nf))
+        if self.nbytes == 0:
+            raise _lib.IAError("mesh adjacency: %d faces are more than %d" % (self.nf, (2 ** 31 - 1) // 6))
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=verts.device)
+        _lib.call("ia_mesh_adjacency_build", _f32(verts), self.faces, self.nv, self.nf, self.ws, self.nbytes)
+
+    def taubin(self, verts, iters, lam, mu):
+        out = torch.empty((self.nv, 3), device=verts.device)
+        _lib.call("ia_mesh_taubin", _f32(verts), self.nv, self.nf, self.ws, self.nbytes, float(lam), float(mu), int(iters), out)
+        return out
+
+    def normals(self, verts):
+        out = torch.empty((self.nv, 3), device=verts.device)
+        _lib.call("ia_mesh_vertex_normals", _f32(verts), self.faces, self.nv, self.nf, self.ws, self.nbytes, out)
+        return out
+
+
+def _f32(t):
+    return t.detach().reshape(-1, 3).float().contiguous()
+
+
+@torch.no_grad()
+def vertex_normals(verts, faces):
+    """normals [nv,3] fp32 from the faces: per vertex the sum of the cross products (twice the area vectors) of its valid faces in
+    ascending face order, in fp64, normalised; the zero vector for a vertex without a valid face"""
+    _lib.require_cuda(verts, faces)
+    return Adjacency(verts, faces).normals(verts)
+
+
+@torch.no_grad()
+def smooth(m, iters=10, lam=0.5, mu=-0.53):
+    """Taubin smoothing of `m`: `iters` times a step lam towards the mean of the neighbours and a step mu (negative: away from it),
+    which damps the lattice's staircase and the hash grid's noise without the shrinkage of plain Laplacian smoothing.  -> a Mesh
+    with new positions, normals from the faces, and the faces and colours of `m`."""
+    _lib.require_cuda(m.verts, m.faces)
+    if int(iters) < 0:
+        raise _lib.IAError("smooth: iters = %d < 0" % iters)
+    adj = Adjacency(m.verts, m.faces)
+    verts = adj.taubin(m.verts, iters, lam, mu)
+    return Mesh(verts, m.faces, adj.normals(verts), m.colors)
+
+
+def cluster_grid(lo, hi, cell):
+    """cells per axis of the clustering grid, max(1, ceil((hi - lo) / cell)) in float64 on the fp32 values, as the library forms them"""
+    lo, hi = np.asarray(lo, np.float32).astype(np.float64), np.asarray(hi, np.float32).astype(np.float64)
+    h = np.float64(np.float32(cell))
+    if not (h > 0 and np.isfinite(h)):
+        raise _lib.IAError("simplify: the cell edge %r must be positive and finite" % (cell,))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise _lib.IAError("simplify: the box is not finite")
+    n = np.maximum(np.ceil((hi - lo) / h), 1.0)
+    if n.prod() > MAX_CLUSTER_CELLS:
+        raise _lib.IAError("simplify: a grid of %.0f x %.0f x %.0f cells is more than 2^27: enlarge the cell" % tuple(n))
+    return [int(x) for x in n]
+
+
+@torch.no_grad()
+def simplify(m, cell, box=None, reg=1e-3):
+    """Vertex clustering of `m` on a grid of edge `cell` over `box` = (lo, hi) (default: the bounding box of the finite vertices,
+    which costs a second host read): one vertex per occupied cell at the minimiser of the cell's quadric pulled towards the
+    members' mean with weight reg * trace, faces with two corners in one cell dropped, colours averaged, normals from the faces.
+    -> a Mesh with the extra attribute `vert_cluster` [nv] int32 (the output vertex of every input vertex, -1 without one).
+    One host read: the two counts."""
+    _lib.require_cuda(m.verts, m.faces, m.colors)
+    verts, colors = _f32(m.verts), _f32(m.colors)
+    faces = m.faces.detach().to(torch.int32).contiguous()
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    if box is None:
+        if nv == 0:
+            lo = hi = np.zeros(3, np.float32)
+        else:
+            fin = torch.isfinite(verts).all(1, keepdim=True)
+            both = torch.stack([torch.where(fin, verts, torch.full_like(verts, float("inf"))).amin(0),
+                                torch.where(fin, verts, torch.full_like(verts, float("-inf"))).amax(0)]).cpu().numpy()
+            lo, hi = (both[0], both[1]) if np.isfinite(both).all() else (np.zeros(3, np.float32), np.zeros(3, np.float32))
+    else:
+        lo, hi = np.asarray(box[0], np.float32).reshape(3), np.asarray(box[1], np.float32).reshape(3)
+    n = cluster_grid(lo, hi, cell)
+    h = np.float32(cell)
+    inv_h = np.float32(1.0 / np.float64(h))
+    if not (float(reg) > 0 and np.isfinite(float(reg))):
+        raise _lib.IAError("simplify: reg = %r must be positive and finite" % (reg,))
+    nb = int(_lib.call("ia_mesh_cluster_workspace_bytes", nv, nf, n[0] * n[1] * n[2]))
+    if nb == 0:
+        raise _lib.IAError("simplify: %d faces are more than %d" % (nf, (2 ** 31 - 1) // 6))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    geo = [float(x) for x in lo] + [float(x) for x in hi] + [float(h), float(inv_h)]
+    _lib.call("ia_mesh_cluster_count", verts, faces, nv, nf, *geo, ws, nb, counts)
+    nv2, nf2 = counts.tolist()
+    v2, c2 = torch.empty((nv2, 3), device=dev), torch.empty((nv2, 3), device=dev)
+    f2 = torch.empty((nf2, 3), dtype=torch.int32, device=dev)
+    vmap = torch.empty(nv, dtype=torch.int32, device=dev)
+    _lib.call("ia_mesh_cluster_emit", verts, faces, colors, nv, nf, *geo, float(reg), ws, nb, v2, nv2, f2, nf2, c2, vmap)
+    out = Mesh(v2, f2, Adjacency(v2, f2).normals(v2), c2)
+    out.vert_cluster = vmap
+    return out

@@ -82,6 +82,18 @@ class AvatarModel(torch.nn.Module):
         from . import mesh as mesh_mod
         return mesh_mod.pose(self.deformer, mesh, batch)
 
+    def simplify_mesh(self, mesh, cell, reg=1e-3):
+        """`mesh` (canonical) with one vertex per occupied cell of edge `cell` of a grid over the field's box, placed by the cell's
+        quadric (`mesh.simplify`; DESIGN.md section 4, "mesh simplification"); the result is canonical again: `pose_mesh` and
+        `render_mesh` take it as they take the input."""
+        from . import mesh as mesh_mod
+        return mesh_mod.simplify(mesh, cell, mesh_mod.field_box(self.net_coarse), reg)
+
+    def smooth_mesh(self, mesh, iters=10, lam=0.5, mu=-0.53):
+        """`mesh` after `iters` Taubin iterations (`mesh.smooth`): positions move, faces and colours are shared."""
+        from . import mesh as mesh_mod
+        return mesh_mod.smooth(mesh, iters, lam, mu)
+
     def render_mesh(self, mesh, batch_or_camera, light=None, cull=True):
         """Pictures of `mesh` by the GPU rasteriser (`Mesh.render`: rgba8, normal8, shaded8, depth, mask on the device).  Given a
         `raster.Camera` the mesh is rendered as it is; given a batch (SMPL parameters plus the key "camera") the canonical mesh is
