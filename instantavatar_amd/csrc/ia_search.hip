@@ -18,6 +18,7 @@
 // tighter, bit-identical) lost by 12 %: more waves inside the loop only lengthen every round trip.  All archived with their
 // numbers under tools/variants/.
 #include "ia_search_dev.h"
+#include "ia_search_tail.h"
 
 // ---------------------------------------------------------------------------
 // a4 + a5 search kernel with LANE REFILL.
@@ -29,7 +30,10 @@
 // small state machine whose loop body is ONE trilinear fetch, and a lane whose
 // solve terminated pulls the next item (wave ballot + one LDS atomic per wave).
 // Items are ordered init-major / point-minor, so lanes refilled together start
-// from neighbouring canonical positions.  Each solve executes exactly the
+// from neighbouring canonical positions.  A wave that runs sparse -- a pull that
+// came back short, or at most 32 solves left at the end of the queue -- keeps its
+// solves in the quad slots that one or two of the fetch's three rounds serve
+// (ia_search_tail.h).  Each solve executes exactly the
 // arithmetic sequence of the reference kernel (fuse_cuda_kernel_fast.cu:268-412).
 // Afterwards the workgroup runs the duplicate filter and either writes the dense
 // reference layout (MODE 0) or compacts the surviving roots (MODE 1).
@@ -150,8 +154,11 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
         int base = 0;
         if (lane == 0) base = atomicAdd(&s_next, __popcll(need));
         base = __shfl(base, 0, 64);
-        if (base >= n_live) queue_empty = true;
-        const int my = base + __popcll(need & ((1ull << lane) - 1ull));
+        int rank = __popcll(need & ((1ull << lane) - 1ull));
+        // a short pull (wave-uniform; the queue is exhausted with it) hands its items out in slot priority 0, 3, 1, 2, so that
+        // a sparse wave needs one or two of the fetch's three rounds (ia_search_tail.h); a full pull keeps the lane order
+        if (base + __popcll(need) > n_live) { queue_empty = true; rank = ia_tail_refill_rank(need, lane); }
+        const int my = base + rank;
         if (!active && my < n_live) {
           item = s_list[my];
           const int init = item >> 7, pt = item & (NP - 1);
@@ -166,7 +173,39 @@ __global__ __launch_bounds__(IA_SEARCH_THREADS) IA_SEARCH_ATTR void k_search(
         }
       }
     }
-    if (!__any(active)) break;
+    const unsigned long long act = __ballot(active);
+    if (act == 0) break;
+    // ---- tail compaction (ia_search_tail.h): at most 32 solves left and one outside the slots of its class -> the survivors
+    // move to those slots, state register by register through ds_bpermute.  Wave-uniform, all 64 lanes enabled (a read from
+    // a lane that EXEC has switched off returns nothing).  The lane-local totals (`counts`, the solves field and the root bit
+    // of `it_solves`) stay where they are: their sums and ORs do not care which lane holds them.
+    if (ia_tail_moves(act)) {
+      // (the lane number through an empty asm: otherwise the lane-only terms of the map are hoisted out of the solver loop and
+      // held in registers across it -- 114 instead of 110 VGPRs)
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      const int src = ia_tail_src(act, ln);
+      const int addr = (src < 0 ? ln : src) << 2;
+#define IA_MOVE_I(v) v = __builtin_amdgcn_ds_bpermute(addr, (int)(v))
+#define IA_MOVE_F(v) v = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)))
+      IA_MOVE_I(item);
+      IA_MOVE_F(xl01.x); IA_MOVE_F(xl01.y); IA_MOVE_F(xl2);
+      IA_MOVE_F(gx01.x); IA_MOVE_F(gx01.y); IA_MOVE_F(gx2);
+      IA_MOVE_F(u01.x); IA_MOVE_F(u01.y); IA_MOVE_F(u2);
+      IA_MOVE_F(Ji.P.x); IA_MOVE_F(Ji.P.y); IA_MOVE_F(Ji.Q.x); IA_MOVE_F(Ji.Q.y); IA_MOVE_F(Ji.R.x); IA_MOVE_F(Ji.R.y);
+      IA_MOVE_F(Ji.S.x); IA_MOVE_F(Ji.S.y); IA_MOVE_F(Ji.J22);
+      int flags = (int)(it_solves & 0xFFu) | (first ? 0x100 : 0);   // the iteration byte and `first` travel with the solve
+      IA_MOVE_I(flags);
+#undef IA_MOVE_I
+#undef IA_MOVE_F
+      active = src >= 0;
+      if (active) {
+        it_solves = (it_solves & ~0xFFu) | (uint32_t)(flags & 0xFF);
+        first = (flags & 0x100) != 0;
+        const int pt = item & (NP - 1);
+        t0 = s_xd[pt][0]; t1 = s_xd[pt][1]; t2 = s_xd[pt][2];
+      }
+    }
     const float xl0 = xl01.x, xl1 = xl01.y;
     const float ix = g.scl[0] * (xl0 + g.off[0]);
     const float iy = g.scl[1] * (xl1 + g.off[1]);
