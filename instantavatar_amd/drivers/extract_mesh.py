@@ -20,7 +20,13 @@ the raster mask.
 --smooth ITERS and --simplify K process the canonical mesh before anything is written ("mesh simplification"):
 first ITERS Taubin iterations, then vertex clustering with quadrics on a grid whose cell edge is K lattice spacings, a spacing
 being max(hi - lo) / (resolution - 1) of the field's box.  The processed mesh is the one that is written, posed and drawn.  One
-line reports `N -> M vertices, N -> M faces` and the wall time of each stage."""
+line reports `N -> M vertices, N -> M faces` and the wall time of each stage.
+
+--texture BLOCK bakes the colour field into a texture atlas over the final mesh, half a block of BLOCK^2 texels per face (DESIGN.md
+section 4, "texture atlas"; `AvatarModel.bake_texture`), after moving every texel's point along the face normal onto the isosurface
+where that lies within --snap lattice spacings (default max(2, --simplify)).  It additionally writes `canonical_textured.obj` / `.mtl` /
+`.png`, with --poses `posed_<i>_textured.obj` (which share that one .mtl and .png), with --render `canonical_front_textured.png` and
+`posed_textured_<i>.png`, and reports the atlas size and the share of texels that found no surface within --snap."""
 import argparse
 import os
 import sys
@@ -52,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--render", type=int, default=0, metavar="SIZE", help="also write SIZE x SIZE pictures of the meshes (GPU rasteriser)")
     ap.add_argument("--smooth", type=int, default=0, metavar="ITERS", help="Taubin iterations on the canonical mesh (0: none)")
     ap.add_argument("--simplify", type=float, default=0.0, metavar="K", help="cluster the vertices on a grid of K >= 1 lattice spacings (0: no)")
+    ap.add_argument("--texture", type=int, default=0, metavar="BLOCK", help="bake a texture atlas with BLOCK in 4 .. 64 texels per block edge (0: no)")
+    ap.add_argument("--snap", type=float, default=None, metavar="K", help="--texture: snap the texels onto the isosurface within K lattice spacings "
+                    "(default max(2, --simplify); 0: no snap)")
     ap.add_argument("--out", default="meshes/out")
     args = ap.parse_args(argv)
     if not args.synthetic and not args.ckpt:
@@ -60,6 +69,10 @@ def main(argv=None):
         ap.error("--smooth %d: the number of iterations cannot be negative" % args.smooth)
     if args.simplify != 0 and not args.simplify >= 1:
         ap.error("--simplify %g: the cell edge is given in lattice spacings and must be at least 1" % args.simplify)
+    if args.texture != 0 and not 4 <= args.texture <= 64:
+        ap.error("--texture %d: the block edge must lie in 4 .. 64 texels" % args.texture)
+    if args.snap is not None and not (args.texture and args.snap >= 0 and np.isfinite(args.snap)):
+        ap.error("--snap needs --texture and a distance >= 0 in lattice spacings")
     import torch
     device = torch.device("cuda:0")
     model, betas = animate.build_model(args, device)
@@ -92,12 +105,30 @@ def main(argv=None):
     if mesh is not extracted:
         print("processed mesh: %d -> %d vertices, %d -> %d faces (%s)"
               % (extracted.verts.shape[0], mesh.verts.shape[0], extracted.faces.shape[0], mesh.faces.shape[0], ", ".join(stages)))
+    textured = None
+    if args.texture:
+        from .. import mesh as mesh_mod
+        lo, hi = mesh_mod.field_box(model.net_coarse)
+        spacing = float((hi.astype(np.float64) - lo.astype(np.float64)).max()) / (args.resolution - 1)
+        snap = (max(2.0, args.simplify) if args.snap is None else args.snap) * spacing
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        textured = model.bake_texture(mesh, block=args.texture, snap=snap, level=args.level)       # (a copy: `mesh` keeps none)
+        tex = textured.texture
+        unsnapped, n_owned = torch.stack([tex.unsnapped, (tex.rgba8[..., 3] != 0).sum().to(torch.int32)]).tolist()   # the one host read
+        textured.to_obj_textured(os.path.join(args.out, "canonical_textured.obj"))
+        print("texture: atlas %d x %d texels in blocks of %d, snap %.4g, %d of %d owned texels (%.2f %%) without a surface crossing (%.3f s, "
+              "file writing included)" % (tex.size, tex.size, tex.block, snap, unsnapped, n_owned, 100.0 * unsnapped / max(n_owned, 1),
+                                          time.perf_counter() - t0))
     if args.render:
         from PIL import Image
         from .. import mesh as mesh_mod, raster
         cam = raster.look_at_box(*mesh_mod.field_box(model.net_coarse), args.render, device)
         front = mesh.render(cam)["rgba8"].cpu().numpy()
         Image.fromarray(animate._bgra_to_rgba(front), "RGBA").save(os.path.join(args.out, "canonical_front.png"))
+        if textured is not None:
+            front = textured.render(cam)["rgba8"].cpu().numpy()
+            Image.fromarray(animate._bgra_to_rgba(front), "RGBA").save(os.path.join(args.out, "canonical_front_textured.png"))
     n = 0
     if args.poses:
         z = np.load(args.poses)
@@ -106,7 +137,7 @@ def main(argv=None):
             poses, trans = poses[:args.max_frames], trans[:args.max_frames]
         seq = animate.AnimateSequence(poses, trans, betas, device, size=args.render or 8)      # (its SMPL parameters; its camera with --render)
         cam = seq.camera() if args.render else None
-        colour, shaded = [], []
+        colour, shaded, painted = [], [], []
         t0 = time.perf_counter()
         for i in range(len(seq)):
             posed = model.pose_mesh(mesh, seq.batch(i, rays=False))
@@ -115,10 +146,17 @@ def main(argv=None):
                 img = posed.render(cam)
                 colour.append(img["rgba8"].cpu().numpy())
                 shaded.append(img["shaded8"].cpu().numpy())
+            if textured is not None:
+                posed.texture = textured.texture
+                posed.to_obj_textured(os.path.join(args.out, "posed_%d_textured.obj" % i), mtllib="canonical_textured.mtl")
+                if cam is not None:
+                    painted.append(posed.render(cam)["rgba8"].cpu().numpy())
         n = len(seq)
         if cam is not None:
             animate.write_frames(colour, args.out, prefix="posed_")
             animate.write_frames(shaded, args.out, prefix="posed_shaded_")
+            if textured is not None:
+                animate.write_frames(painted, args.out, prefix="posed_textured_")
         print("posed meshes: %d frames in %.3f s (file writing included)" % (n, time.perf_counter() - t0))
     print("wrote canonical.%s%s to %s" % (args.format, " and %d posed meshes" % n if n else "", args.out))
     return 0

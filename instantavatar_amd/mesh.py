@@ -3,7 +3,9 @@
 connected component, per-vertex colours and normals from the field, forward skinning into a posed frame, and PLY / OBJ
 writers (numpy only).  `AvatarModel.extract_mesh` / `AvatarModel.pose_mesh` are the public entry points.  `simplify`, `smooth` and
 `vertex_normals` process a mesh afterwards (csrc/ia_meshops.hip, include/instantavatar_hip_meshops.h; DESIGN.md section 4, "mesh
-simplification"): vertex clustering with quadrics, Taubin smoothing, normals from the faces.
+simplification"): vertex clustering with quadrics, Taubin smoothing, normals from the faces.  A mesh may carry a texture atlas baked
+from the colour field (`texture`, `AvatarModel.bake_texture`; DESIGN.md section 4, "texture atlas"): `pose` keeps it, `smooth` and
+`simplify` return meshes without one, since the atlas belongs to the faces and positions it was baked over.
 
 The level is OURS: the reference ships a marching-cubes helper it never calls, whose default level 0 is meant for signed
 distances; sigma = 10 is a density at which a 1 cm step is already ~10 % opaque.  It is a parameter."""
@@ -23,11 +25,16 @@ class Mesh:
 
     def __init__(self, verts, faces, normals, colors):
         self.verts, self.faces, self.normals, self.colors = verts, faces, normals, colors
+        #: a `texture.Texture` baked over these faces (`AvatarModel.bake_texture`), or None: the mesh carries vertex colours only
+        self.texture = None
 
     def render(self, camera, light=None, cull=True):
         """8-bit pictures of the mesh under `camera` (`raster.Camera`) by the GPU rasteriser: a dict of device tensors rgba8,
-        normal8, shaded8 [H,W,4] uint8, depth [H,W], mask [H,W] (and face_id) -- see `raster.render`."""
+        normal8, shaded8 [H,W,4] uint8, depth [H,W], mask [H,W] (and face_id) -- see `raster.render`.  A mesh with a texture is
+        drawn with it (`raster.render_textured`, which adds `uv`)."""
         from . import raster
+        if self.texture is not None:
+            return raster.render_textured(self, camera, light, cull)
         return raster.render(self, camera, light, cull)
 
     def simplify(self, cell, box=None, reg=1e-3):
@@ -74,6 +81,36 @@ class Mesh:
             np.savetxt(out, n.astype(np.float64), fmt="vn %.9g %.9g %.9g")
             g = f.astype(np.int64) + 1
             np.savetxt(out, np.stack([g[:, 0], g[:, 0], g[:, 1], g[:, 1], g[:, 2], g[:, 2]], 1), fmt="f %d//%d %d//%d %d//%d")
+
+    def to_obj_textured(self, path, mtllib=None):
+        """Wavefront OBJ with the baked texture: `path` holds `mtllib`, `v x y z`, `vn`, three `vt` per face (corner (x, y) in
+        continuous texels -> (x / T, 1 - y / T)), `usemtl` and `f a/ta/a b/tb/b c/tc/c` (1-based); `<stem>.mtl` next to it names
+        `<stem>.png`, the atlas in RGB order without alpha, row 0 = y = 0.  mtllib: the .mtl of another mesh in the same directory;
+        only the OBJ is written then and names it -- posed meshes share the canonical mesh's material and picture."""
+        import os
+        if self.texture is None:
+            raise _lib.IAError("to_obj_textured: the mesh has no texture (AvatarModel.bake_texture / texture.bake make one)")
+        v, f, n, _ = self._host()
+        if len(f) != self.texture.uv.shape[0]:
+            raise _lib.IAError("to_obj_textured: the texture was baked over %d faces, the mesh has %d" % (self.texture.uv.shape[0], len(f)))
+        mtl = os.path.splitext(path if mtllib is None else mtllib)[0] + ".mtl"
+        if mtllib is None:
+            from PIL import Image
+            png = os.path.splitext(path)[0] + ".png"
+            Image.fromarray(np.ascontiguousarray(self.texture.rgba8.detach().cpu().numpy()[..., 2::-1]), "RGB").save(png)
+            with open(mtl, "w") as out:
+                out.write("# instantavatar_amd texture: %d x %d texels, blocks of %d\nnewmtl avatar\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\n"
+                          "map_Kd %s\n" % (self.texture.size, self.texture.size, self.texture.block, os.path.basename(png)))
+        with open(path, "w") as out:
+            out.write("# instantavatar_amd mesh: %d vertices, %d faces, textured\nmtllib %s\n" % (len(v), len(f), os.path.basename(mtl)))
+            np.savetxt(out, v.astype(np.float64), fmt="v %.9g %.9g %.9g")
+            np.savetxt(out, n.astype(np.float64), fmt="vn %.9g %.9g %.9g")
+            np.savetxt(out, self.texture.vt().reshape(-1, 2), fmt="vt %.9g %.9g")
+            out.write("usemtl avatar\n")
+            g = f.astype(np.int64) + 1
+            t = np.arange(3 * len(f), dtype=np.int64).reshape(-1, 3) + 1
+            np.savetxt(out, np.stack([g[:, 0], t[:, 0], g[:, 0], g[:, 1], t[:, 1], g[:, 1], g[:, 2], t[:, 2], g[:, 2]], 1),
+                       fmt="f %d/%d/%d %d/%d/%d %d/%d/%d")
 
 
 def field_box(net):
@@ -209,7 +246,9 @@ def pose(deformer, mesh, batch):
         # n = -M^{-T} g with g = -n_c: only the direction of the gradient enters
         idx = torch.arange(nv, dtype=torch.int32, device=dev)
         _lib.call("ia_normals_from_gradient", verts, (-mesh.normals).contiguous(), idx, nv, None, vJ, grid, w2s, nv, normals)
-    return Mesh(xd, mesh.faces, normals, mesh.colors)
+    out = Mesh(xd, mesh.faces, normals, mesh.colors)
+    out.texture = mesh.texture          # the faces are shared, so one bake serves every pose
+    return out
 
 
 # ---- processing of a mesh: csrc/ia_meshops.hip --------------------------------------------------------------------------------------

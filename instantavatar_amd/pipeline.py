@@ -94,6 +94,35 @@ class AvatarModel(torch.nn.Module):
         from . import mesh as mesh_mod
         return mesh_mod.smooth(mesh, iters, lam, mu)
 
+    def bake_texture(self, mesh, block=8, snap=None, level=10.0, steps=9, chunk=1 << 21):
+        """`mesh` (canonical) with `.texture` set: the colour field baked into an atlas with half a block of `block`^2 texels per face
+        (`texture.bake`; DESIGN.md section 4, "texture atlas").  Every texel's point is first moved along the face normal onto the
+        isosurface sigma = `level` when that lies within `snap` (None: twice the mean edge length of the mesh, which costs one host
+        read; 0: no snap); colours are the field's rgb without a view direction, as the vertex colours.  `pose_mesh` carries the
+        texture along, `Mesh.render` and `Mesh.to_obj_textured` use it."""
+        import copy
+        import torch
+        from . import _lib, texture
+        net = self.net_coarse
+        _lib.require_cuda(net.center, mesh.verts, mesh.faces)
+        if snap is None:
+            v, f = mesh.verts.detach().float(), mesh.faces.detach().long()
+            nv = v.shape[0]
+            ok = ((f >= 0) & (f < nv)).all(1) if nv else torch.zeros(f.shape[0], dtype=torch.bool, device=f.device)
+            tri = v[f[ok]]                                                                     # [n,3,3]
+            edges = (tri - tri.roll(-1, 1)).double().norm(dim=-1)
+            edges = edges[torch.isfinite(edges)]
+            snap = 2.0 * float(edges.mean()) if edges.numel() else 0.0
+
+        def sample(pts):
+            n = pts.shape[0]
+            rgb, sigma = torch.empty((n, 3), device=pts.device), torch.empty(n, device=pts.device)
+            _lib.call("ia_field_fwd", pts, n, None, net.field_desc(n), rgb, sigma)
+            return rgb, sigma
+        out = copy.copy(mesh)                  # the tensors are shared, the input keeps its `texture`
+        out.texture = texture.bake(mesh, sample, block, snap, level, steps, chunk)
+        return out
+
     def render_mesh(self, mesh, batch_or_camera, light=None, cull=True):
         """Pictures of `mesh` by the GPU rasteriser (`Mesh.render`: rgba8, normal8, shaded8, depth, mask on the device).  Given a
         `raster.Camera` the mesh is rendered as it is; given a batch (SMPL parameters plus the key "camera") the canonical mesh is

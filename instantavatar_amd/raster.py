@@ -114,3 +114,42 @@ def render(mesh, camera, light=None, cull=True):
     _lib.call("ia_pack_rgba8", rgb, frame.mask.reshape(R).float(), R, rgba8)
     _lib.call("ia_pack_normals8", normal, camera.rays_d(), light, R, normal8, shaded8)
     return dict(rgba8=rgba8, normal8=normal8, shaded8=shaded8, depth=frame.depth, mask=frame.mask, face_id=frame.face_id)
+
+
+@torch.no_grad()
+def render_textured(mesh, camera, light=None, cull=True):
+    """`Mesh.render` of a mesh with a `texture`: the dict of `render` with rgba8 holding the atlas colours filtered at the
+    interpolated corner coordinates (ia_tex_sample), plus uv [H,W,2] fp32 (continuous texel coordinates, 0 = empty).  Texture
+    coordinates belong to corners, not vertices, so the unshared copy verts[faces] is rasterised with faces = arange: the same
+    position bits in the same face order, hence the face_id and depth of `render`.  One resolve of 5 channels: uv and the
+    camera-frame normal."""
+    from . import texture as texture_mod
+    tex = mesh.texture
+    if tex is None:
+        raise _lib.IAError("render_textured: the mesh has no texture (AvatarModel.bake_texture / texture.bake make one)")
+    _lib.require_cuda(mesh.verts, mesh.faces, mesh.normals, tex.atlas, tex.uv, camera.w2c, light)
+    H, W = camera.H, camera.W
+    dev = mesh.verts.device
+    verts = mesh.verts.detach().reshape(-1, 3).float()
+    faces = mesh.faces.detach().reshape(-1, 3).long()
+    nv, nf = verts.shape[0], faces.shape[0]
+    if tex.uv.shape[0] != nf:
+        raise _lib.IAError("render_textured: the texture was baked over %d faces, the mesh has %d" % (tex.uv.shape[0], nf))
+    n_cam = mesh.normals.detach().float() @ camera.w2c[:3, :3].T           # world -> camera frame (a rotation)
+    # a face with an index outside [0, nv) is skipped by `render`: here its corners become invalid vertices
+    bad = ((faces < 0) | (faces >= nv)).any(1, keepdim=True).expand(nf, 3).reshape(-1)
+    idx = faces.clamp(0, max(nv - 1, 0)).reshape(-1)
+    corners = torch.where(bad[:, None], torch.full((1, 3), float("nan"), device=dev), verts[idx]) if nv else verts.new_zeros((0, 3))
+    attrs = torch.cat([tex.uv.reshape(-1, 2).float(), n_cam[idx]], 1) if nv else verts.new_zeros((0, 5))
+    frame = rasterize(corners, torch.arange(3 * nf, dtype=torch.int32, device=dev).reshape(-1, 3), camera, attrs, cull)
+    R = H * W
+    uv = frame.attrs[..., :2].contiguous()
+    mask = frame.mask.reshape(R).float()
+    rgb = texture_mod.sample(tex, uv.reshape(R, 2), mask)
+    minus_n = (-frame.attrs[..., 2:]).reshape(R, 3).contiguous()
+    normal = torch.empty((R, 3), device=dev)
+    _lib.call("ia_unit_negative", minus_n, R, normal)
+    rgba8, normal8, shaded8 = (torch.empty((H, W, 4), dtype=torch.uint8, device=dev) for _ in range(3))
+    _lib.call("ia_pack_rgba8", rgb, mask, R, rgba8)
+    _lib.call("ia_pack_normals8", normal, camera.rays_d(), light, R, normal8, shaded8)
+    return dict(rgba8=rgba8, normal8=normal8, shaded8=shaded8, depth=frame.depth, mask=frame.mask, face_id=frame.face_id, uv=uv)
