@@ -86,6 +86,9 @@ MESHOPS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_h
 # and the texture-atlas entry points (csrc/ia_texture.hip): `texture_declarations`
 TEXTURE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_texture.h")
 
+# and the rigged-export entry points (csrc/ia_rig.hip): `rig_declarations`
+RIG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_rig.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -329,6 +332,25 @@ def texture_declarations():
     return _texture_decls
 
 
+_rig_decls = None
+
+
+def rig_declarations():
+    """parse_header of include/instantavatar_hip_rig.h, read once: a twelfth table, bound in `lib()` and reachable through
+    `call` like the other eleven; its names are disjoint from theirs."""
+    global _rig_decls
+    if _rig_decls is None:
+        d = _parse_file(RIG_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
+                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
+                                | set(texture_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_rig.h declares %s, which another header declares already" % ", ".join(both))
+        _rig_decls = d
+    return _rig_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -369,7 +391,7 @@ def lib():
         for name, d in list(declarations().items()) + list(io_declarations().items()) + list(normals_declarations().items()) \
                 + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()) \
                 + list(silhouette_declarations().items()) + list(masks_declarations().items()) + list(overlay_declarations().items()) \
-                + list(meshops_declarations().items()) + list(texture_declarations().items()):
+                + list(meshops_declarations().items()) + list(texture_declarations().items()) + list(rig_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -457,7 +479,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

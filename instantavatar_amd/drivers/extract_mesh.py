@@ -26,7 +26,12 @@ line reports `N -> M vertices, N -> M faces` and the wall time of each stage.
 section 4, "texture atlas"; `AvatarModel.bake_texture`), after moving every texel's point along the face normal onto the isosurface
 where that lies within --snap lattice spacings (default max(2, --simplify)).  It additionally writes `canonical_textured.obj` / `.mtl` /
 `.png`, with --poses `posed_<i>_textured.obj` (which share that one .mtl and .png), with --render `canonical_front_textured.png` and
-`posed_textured_<i>.png`, and reports the atlas size and the share of texels that found no surface within --snap."""
+`posed_textured_<i>.png`, and reports the atlas size and the share of texels that found no surface within --snap.
+
+--rig K additionally writes `avatar.glb`, a glTF 2.0 binary of the final mesh with a skin of 24 joints and the K (1 .. 24) largest
+skinning weights per vertex ("rigged export"; `AvatarModel.rig_mesh`, `Mesh.to_glb`): textured with --texture,
+vertex-coloured without, and with --poses animated by the pose track at --fps key frames per second.  With --poses one line reports
+the maximum and the mean distance, over all frames and vertices, between the rig's skinning and the posed meshes."""
 import argparse
 import os
 import sys
@@ -61,6 +66,8 @@ def main(argv=None):
     ap.add_argument("--texture", type=int, default=0, metavar="BLOCK", help="bake a texture atlas with BLOCK in 4 .. 64 texels per block edge (0: no)")
     ap.add_argument("--snap", type=float, default=None, metavar="K", help="--texture: snap the texels onto the isosurface within K lattice spacings "
                     "(default max(2, --simplify); 0: no snap)")
+    ap.add_argument("--rig", type=int, default=0, metavar="K", help="also write avatar.glb: the mesh rigged with K in 1 .. 24 influences per vertex (0: no)")
+    ap.add_argument("--fps", type=float, default=30.0, help="--rig with --poses: key frames per second of the glTF animation")
     ap.add_argument("--out", default="meshes/out")
     args = ap.parse_args(argv)
     if not args.synthetic and not args.ckpt:
@@ -73,6 +80,10 @@ def main(argv=None):
         ap.error("--texture %d: the block edge must lie in 4 .. 64 texels" % args.texture)
     if args.snap is not None and not (args.texture and args.snap >= 0 and np.isfinite(args.snap)):
         ap.error("--snap needs --texture and a distance >= 0 in lattice spacings")
+    if args.rig != 0 and not 1 <= args.rig <= 24:
+        ap.error("--rig %d: the number of influences per vertex must lie in 1 .. 24" % args.rig)
+    if not (args.fps > 0 and np.isfinite(args.fps)):
+        ap.error("--fps %g: the frame rate must be positive" % args.fps)
     import torch
     device = torch.device("cuda:0")
     model, betas = animate.build_model(args, device)
@@ -130,6 +141,8 @@ def main(argv=None):
             front = textured.render(cam)["rgba8"].cpu().numpy()
             Image.fromarray(animate._bgra_to_rgba(front), "RGBA").save(os.path.join(args.out, "canonical_front_textured.png"))
     n = 0
+    rig = model.rig_mesh(mesh, influences=args.rig) if args.rig else None
+    animation = None
     if args.poses:
         z = np.load(args.poses)
         poses, trans = z["poses"].astype(np.float32), z["trans"].astype(np.float32)
@@ -139,8 +152,17 @@ def main(argv=None):
         cam = seq.camera() if args.render else None
         colour, shaded, painted = [], [], []
         t0 = time.perf_counter()
+        if rig is not None:
+            from .. import rig as rig_mod
+            bones, quat, root_t = rig_mod.track(model.deformer, seq.thetas, seq.transl)
+            animation = (quat, root_t)
+            skinned = rig_mod.skin(rig, mesh, bones)[0]
+            dev_max, dev_sum = torch.zeros((), dtype=torch.float64, device=device), torch.zeros((), dtype=torch.float64, device=device)
         for i in range(len(seq)):
             posed = model.pose_mesh(mesh, seq.batch(i, rays=False))
+            if rig is not None:
+                d_max, d_mean = rig_mod.deviation(skinned[i:i + 1], posed.verts[None])
+                dev_max, dev_sum = torch.maximum(dev_max, d_max[0]), dev_sum + d_mean[0]
             write(posed, "posed_%d" % i)
             if cam is not None:
                 img = posed.render(cam)
@@ -158,6 +180,13 @@ def main(argv=None):
             if textured is not None:
                 animate.write_frames(painted, args.out, prefix="posed_textured_")
         print("posed meshes: %d frames in %.3f s (file writing included)" % (n, time.perf_counter() - t0))
+        if rig is not None and n:
+            print("rig: %d influences per vertex deviate from the posed meshes by at most %.3e, %.3e on average over %d frames"
+                  % (args.rig, float(dev_max), float(dev_sum) / n, n))
+    if rig is not None:
+        (textured if textured is not None else mesh).to_glb(os.path.join(args.out, "avatar.glb"), rig, animation, args.fps)
+        print("rig: avatar.glb with %d vertices, 24 joints, %d influences%s%s" % (
+            mesh.verts.shape[0], args.rig, ", textured" if textured is not None else "", ", %d key frames at %g per second" % (n, args.fps) if n else ""))
     print("wrote canonical.%s%s to %s" % (args.format, " and %d posed meshes" % n if n else "", args.out))
     return 0
 

@@ -5,7 +5,8 @@ writers (numpy only).  `AvatarModel.extract_mesh` / `AvatarModel.pose_mesh` are 
 `vertex_normals` process a mesh afterwards (csrc/ia_meshops.hip, include/instantavatar_hip_meshops.h; DESIGN.md section 4, "mesh
 simplification"): vertex clustering with quadrics, Taubin smoothing, normals from the faces.  A mesh may carry a texture atlas baked
 from the colour field (`texture`, `AvatarModel.bake_texture`; DESIGN.md section 4, "texture atlas"): `pose` keeps it, `smooth` and
-`simplify` return meshes without one, since the atlas belongs to the faces and positions it was baked over.
+`simplify` return meshes without one, since the atlas belongs to the faces and positions it was baked over.  `Mesh.to_glb` writes
+the mesh, a rig (`rig.Rig`) and a pose track as one glTF binary ("rigged export").
 
 The level is OURS: the reference ships a marching-cubes helper it never calls, whose default level 0 is meant for signed
 distances; sigma = 10 is a density at which a 1 cm step is already ~10 % opaque.  It is a parameter."""
@@ -111,6 +112,36 @@ class Mesh:
             t = np.arange(3 * len(f), dtype=np.int64).reshape(-1, 3) + 1
             np.savetxt(out, np.stack([g[:, 0], t[:, 0], g[:, 0], g[:, 1], t[:, 1], g[:, 1], g[:, 2], t[:, 2], g[:, 2]], 1),
                        fmt="f %d/%d/%d %d/%d/%d %d/%d/%d")
+
+    def to_glb(self, path, rig=None, animation=None, fps=30):
+        """glTF 2.0 binary (`gltf.write_glb`; DESIGN.md section 4, "rigged export"): the mesh with its texture when it carries one
+        (un-indexed, the atlas embedded as the PNG `to_obj_textured` writes) and with its vertex colours otherwise; rig: a
+        `rig.Rig` of this (canonical) mesh -> a skin of 24 joints; animation: (quat [F,24,4], root_t [F,3]) of `rig.track` -> the
+        pose track as key frames i / fps.  Zero normals are replaced by `vertex_normals` of the mesh."""
+        from . import gltf
+        v, f, n, rgb8 = self._host()
+        if rig is None and animation is not None:
+            raise _lib.IAError("to_glb: an animation needs a rig (AvatarModel.rig_mesh / rig.build make one)")
+        kw = {}
+        if not (np.isfinite(n).all() and (np.abs(n).max(1, initial=0.0) > 0).all()) and self.verts.is_cuda:
+            kw["fallback_normals"] = vertex_normals(self.verts, self.faces).cpu().numpy()
+        if self.texture is not None:
+            if len(f) != self.texture.uv.shape[0]:
+                raise _lib.IAError("to_glb: the texture was baked over %d faces, the mesh has %d" % (self.texture.uv.shape[0], len(f)))
+            vt = self.texture.vt()
+            kw["corner_uv"] = np.stack([vt[..., 0], 1.0 - vt[..., 1]], -1)       # glTF's origin is top-left, as the PNG's
+            kw["image"] = np.ascontiguousarray(self.texture.rgba8.detach().cpu().numpy()[..., 2::-1])
+        else:
+            kw["colors8"] = rgb8
+        if rig is not None:
+            host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+            if rig.joints.shape[0] != len(v):
+                raise _lib.IAError("to_glb: the rig has %d vertices, the mesh %d" % (rig.joints.shape[0], len(v)))
+            kw.update(joints=host(rig.joints), weights=host(rig.weights), parents=rig.parents, rest_translation=rig.rest_translation,
+                      cano_quat=rig.cano_quat, inverse_bind=rig.inverse_bind)
+            if animation is not None:
+                kw.update(animation=tuple(host(a) for a in animation), fps=fps)
+        gltf.write_glb(path, v, f, n, **kw)
 
 
 def field_box(net):

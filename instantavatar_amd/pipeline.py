@@ -123,6 +123,20 @@ class AvatarModel(torch.nn.Module):
         out.texture = texture.bake(mesh, sample, block, snap, level, steps, chunk)
         return out
 
+    def rig_mesh(self, mesh, influences=4):
+        """The standard rig of `mesh` (canonical): per vertex the `influences` largest skinning weights of the deformer's weight
+        volume and their joints, plus the skeleton's rest offsets, canonical rotations and inverse bind matrices (`rig.build` ->
+        `rig.Rig`; DESIGN.md section 4, "rigged export").  `Mesh.to_glb(path, rig)` exports it.  SNARF deformer only."""
+        from . import rig as rig_mod
+        return rig_mod.build(self.deformer, mesh, influences)
+
+    def skin_rigged(self, mesh, rig, poses72, transl=None):
+        """`mesh` (canonical) skinned with `rig` into every frame of a pose track -- poses72 [F,72], transl [F,3] on the device -- in
+        the world frame: (verts [F,n,3], normals [F,n,3]), two launches for the whole track (`rig.track`, `rig.skin`).  With 24
+        influences the positions are `pose_mesh`'s up to rounding; the normals are M_3x3 n normalised, what a glTF viewer draws."""
+        from . import rig as rig_mod
+        return rig_mod.skin(rig, mesh, rig_mod.track(self.deformer, poses72, transl)[0])
+
     def render_mesh(self, mesh, batch_or_camera, light=None, cull=True):
         """Pictures of `mesh` by the GPU rasteriser (`Mesh.render`: rgba8, normal8, shaded8, depth, mask on the device).  Given a
         `raster.Camera` the mesh is rendered as it is; given a batch (SMPL parameters plus the key "camera") the canonical mesh is
