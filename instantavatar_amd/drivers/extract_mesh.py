@@ -31,7 +31,13 @@ where that lies within --snap lattice spacings (default max(2, --simplify)).  It
 --rig K additionally writes `avatar.glb`, a glTF 2.0 binary of the final mesh with a skin of 24 joints and the K (1 .. 24) largest
 skinning weights per vertex ("rigged export"; `AvatarModel.rig_mesh`, `Mesh.to_glb`): textured with --texture,
 vertex-coloured without, and with --poses animated by the pose track at --fps key frames per second.  With --poses one line reports
-the maximum and the mean distance, over all frames and vertices, between the rig's skinning and the posed meshes."""
+the maximum and the mean distance, over all frames and vertices, between the rig's skinning and the posed meshes.
+
+--deviation [SAMPLES] (with --smooth or --simplify) measures how far the processed mesh lies from the extracted one (DESIGN.md section 4,
+"surface distance"; `Mesh.compare`): SAMPLES surface samples per direction (default 100 000), one `deviation:` line with the mean, the
+95th percentile and the maximum of the distances both ways in metres and in lattice spacings, and `deviation.json` with the whole
+report.  With --render it also writes `deviation_front.png`: the EXTRACTED mesh under the camera of `canonical_front.png`, every
+vertex coloured by its distance to the final mesh, blue (0) over green to red (2 lattice spacings and more)."""
 import argparse
 import os
 import sys
@@ -68,8 +74,14 @@ def main(argv=None):
                     "(default max(2, --simplify); 0: no snap)")
     ap.add_argument("--rig", type=int, default=0, metavar="K", help="also write avatar.glb: the mesh rigged with K in 1 .. 24 influences per vertex (0: no)")
     ap.add_argument("--fps", type=float, default=30.0, help="--rig with --poses: key frames per second of the glTF animation")
+    ap.add_argument("--deviation", type=int, nargs="?", const=100000, default=None, metavar="SAMPLES", help="with --smooth / --simplify: report the "
+                    "distance between the extracted and the processed mesh from SAMPLES surface samples per direction (default 100000)")
     ap.add_argument("--out", default="meshes/out")
     args = ap.parse_args(argv)
+    if args.deviation is not None and not (args.smooth or args.simplify):
+        ap.error("--deviation compares the extracted mesh with the processed one: it needs --smooth or --simplify")
+    if args.deviation is not None and args.deviation < 0:
+        ap.error("--deviation %d: the number of samples cannot be negative" % args.deviation)
     if not args.synthetic and not args.ckpt:
         ap.error("--ckpt is required unless --synthetic is given")
     if args.smooth < 0:
@@ -116,6 +128,29 @@ def main(argv=None):
     if mesh is not extracted:
         print("processed mesh: %d -> %d vertices, %d -> %d faces (%s)"
               % (extracted.verts.shape[0], mesh.verts.shape[0], extracted.faces.shape[0], mesh.faces.shape[0], ", ".join(stages)))
+    if args.deviation is not None:
+        import json
+        from .. import mesh as mesh_mod, meshdist
+        lo, hi = mesh_mod.field_box(model.net_coarse)
+        spacing = float((hi.astype(np.float64) - lo.astype(np.float64)).max()) / (args.resolution - 1)
+        report = extracted.compare(mesh, samples=args.deviation)
+        ab, ba = report["a_to_b"], report["b_to_a"]
+        print("deviation: extracted -> processed mean %.3e p95 %.3e max %.3e m (%.3f / %.3f / %.3f spacings), processed -> extracted mean %.3e "
+              "p95 %.3e max %.3e m (%.3f / %.3f / %.3f spacings), %d samples each way"
+              % (ab["mean"], ab["p95"], ab["max"], ab["mean"] / spacing, ab["p95"] / spacing, ab["max"] / spacing, ba["mean"], ba["p95"],
+                 ba["max"], ba["mean"] / spacing, ba["p95"] / spacing, ba["max"] / spacing, args.deviation))
+        report.update(resolution=args.resolution, spacing=spacing, samples=args.deviation,
+                      extracted=dict(vertices=int(extracted.verts.shape[0]), faces=int(extracted.faces.shape[0])),
+                      processed=dict(vertices=int(mesh.verts.shape[0]), faces=int(mesh.faces.shape[0])))
+        with open(os.path.join(args.out, "deviation.json"), "w") as out:
+            json.dump(meshdist.report_json(report), out, indent=1, sort_keys=True)
+        if args.render:
+            from PIL import Image
+            from .. import raster
+            cam = raster.look_at_box(lo, hi, args.render, device)
+            painted = mesh_mod.Mesh(extracted.verts, extracted.faces, extracted.normals,
+                                    meshdist.heat(extracted.distance_to(mesh)["dist"], 2.0 * spacing))
+            Image.fromarray(animate._bgra_to_rgba(painted.render(cam)["rgba8"].cpu().numpy()), "RGBA").save(os.path.join(args.out, "deviation_front.png"))
     textured = None
     if args.texture:
         from .. import mesh as mesh_mod

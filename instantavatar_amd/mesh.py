@@ -6,7 +6,9 @@ writers (numpy only).  `AvatarModel.extract_mesh` / `AvatarModel.pose_mesh` are 
 simplification"): vertex clustering with quadrics, Taubin smoothing, normals from the faces.  A mesh may carry a texture atlas baked
 from the colour field (`texture`, `AvatarModel.bake_texture`; DESIGN.md section 4, "texture atlas"): `pose` keeps it, `smooth` and
 `simplify` return meshes without one, since the atlas belongs to the faces and positions it was baked over.  `Mesh.to_glb` writes
-the mesh, a rig (`rig.Rig`) and a pose track as one glTF binary ("rigged export").
+the mesh, a rig (`rig.Rig`) and a pose track as one glTF binary ("rigged export").  `Mesh.distance_to` and
+`Mesh.compare` measure the distance to another mesh, `Mesh.from_ply` / `Mesh.from_obj` read the written files back (`meshdist`;
+DESIGN.md section 4, "surface distance").
 
 The level is OURS: the reference ships a marching-cubes helper it never calls, whose default level 0 is meant for signed
 distances; sigma = 10 is a density at which a 1 cm step is already ~10 % opaque.  It is a parameter."""
@@ -45,6 +47,35 @@ class Mesh:
     def smooth(self, iters=10, lam=0.5, mu=-0.53):
         """`smooth(self, iters, lam, mu)`: Taubin smoothing of the positions"""
         return smooth(self, iters, lam, mu)
+
+    def distance_to(self, other):
+        """per vertex of this mesh the closest point of `other` (`meshdist.closest`): a dict of dist [nv], face [nv], bary [nv,3] and
+        point [nv,3]; a vertex with a non-finite coordinate gets dist = NaN and face = -1"""
+        from . import meshdist
+        return meshdist.closest(self.verts, other)
+
+    def compare(self, other, samples=100000, taus=()):
+        """`meshdist.compare(self, other, samples, taus)`: distances both ways, Chamfer, Hausdorff, normal consistency, F-scores"""
+        from . import meshdist
+        return meshdist.compare(self, other, samples, taus)
+
+    @classmethod
+    def from_ply(cls, path, device):
+        """a Mesh on `device` from a PLY file: what `to_ply` writes (verts, faces and normals come back with the same bytes; colours in
+        their 8-bit steps), or a plain binary little-endian / ASCII PLY (`meshdist.read_ply`)"""
+        from . import meshdist
+        if not str(path).lower().endswith(".ply"):
+            raise _lib.IAError("from_ply: %s is not a .ply file" % path)
+        return meshdist.load_mesh(path, device)
+
+    @classmethod
+    def from_obj(cls, path, device):
+        """a Mesh on `device` from a Wavefront OBJ: what `to_obj` / `to_obj_textured` write (without the texture), or a plain OBJ with
+        `v` / `f` lines (`meshdist.read_obj`)"""
+        from . import meshdist
+        if not str(path).lower().endswith(".obj"):
+            raise _lib.IAError("from_obj: %s is not a .obj file" % path)
+        return meshdist.load_mesh(path, device)
 
     def _host(self):
         f = lambda t: t.detach().cpu().numpy()
