@@ -86,6 +86,7 @@ class DeviceFrames:
         _lib.require_cuda(images_u8, masks)
         N, H, W, _ = images_u8.shape
         self.N, self.H, self.W = N, H, W
+        self.K, self.c2w = np.asarray(K, np.float64).copy(), np.asarray(c2w, np.float64).copy()      # host copies: `camera()`
         self.rays_o, self.rays_d = make_rays(K, c2w, H, W, images_u8.device)
         dev = images_u8.device
         self.smpl_params = {k: torch.as_tensor(np.asarray(v, np.float32), device=dev) for k, v in smpl_params.items()}
@@ -160,6 +161,15 @@ class DeviceFrames:
 
     def __len__(self):
         return self.N
+
+    def camera(self, near=0.05):
+        """the sequence's camera for the mesh rasteriser (`raster.Camera`): its K, w2c = c2w^-1 on the device, its image size -- the
+        camera its rays were made from, so a raster frame of a posed mesh overlays the frame's image"""
+        from ..raster import Camera
+        c2w = np.eye(4)
+        c2w[:self.c2w.shape[0], :] = self.c2w                      # ([3,4] or [4,4])
+        w2c = torch.as_tensor(np.linalg.inv(c2w), dtype=torch.float32, device=self.images.device)
+        return Camera(self.K, w2c, self.H, self.W, near=near)
 
     def frame(self, idx):
         """PeopleSnapshotDataset.__getitem__ for split "val" / "test" (peoplesnapshot.py:112-125): the WHOLE frame, white

@@ -55,6 +55,33 @@ def synthetic_test_set(device, teacher, res, n_frames, pose_noise, transl_noise,
     return frames, true, start
 
 
+def synthetic_photo_set(device, teacher, res, n_frames, held_out=False):
+    """Frames of the synthetic subject for a photo texture (`extract_mesh --photo --synthetic`): `n_frames` renderings of `teacher` at
+    `res`^2 along the procedural pose track with the global orientation turned about the vertical axis through a full circle in
+    equal steps, so that every side of the body is seen; the TRUE poses, no noise.  held_out: the same track turned by half a step
+    further and half a frame later -- poses between those of the set.  -> DeviceFrames (8-bit images in the model's channel order,
+    masks alpha > 0.5, the camera of `synthetic_test_set`)."""
+    from ..datasets.device_frames import DeviceFrames
+    from ..utils.sampler import EdgeSampler
+    from .novel_view import matrix_to_rotvec, rotvec_to_matrix
+    n = int(n_frames)
+    poses, tr = synthetic.procedural_pose_track(2 * max(n, 4))
+    poses, tr = poses[int(bool(held_out))::2][:n].copy(), tr[int(bool(held_out))::2][:n].copy()
+    for f in range(n):
+        turn = rotvec_to_matrix([0.0, 2 * np.pi * (f + (0.5 if held_out else 0.0)) / n, 0.0])
+        poses[f, :3] = matrix_to_rotvec(turn @ rotvec_to_matrix(poses[f, :3]))
+    imgs, masks = [], []
+    with torch.no_grad():
+        for f in range(n):
+            rgb, _, alpha, _ = teacher.render_image_fast(make_batch(device, res, poses[f], tr[f]), (res, res))
+            imgs.append(ev.to_u8(rgb[0].clamp(0, 1) * 255))
+            masks.append((alpha[0] > 0.5).float())
+    true = dict(betas=np.zeros((1, 10), np.float32), body_pose=poses[:, 3:].copy(), global_orient=poses[:, :3].copy(), transl=tr.copy())
+    K = np.array([[2000.0 * res / 1080, 0, res / 2], [0, 2000.0 * res / 1080, res / 2], [0, 0, 1]])
+    sampler = EdgeSampler(num_sample=4096, ratio_mask=0.6, ratio_edge=0.3, kernel_size=16)          # confs/sampler/edge.yaml
+    return DeviceFrames(torch.stack(imgs), torch.stack(masks), K, np.eye(4), true, sampler)
+
+
 def refine_test_frames(model, frames, epochs, smpl_lr=1e-5, seed=42, log=None, check_val_every_n_epoch=10):
     """eval.py:70-91 (`trainer.fit` on the test split with only `SMPL_param` trainable): `epochs` passes over the frames,
     training_step with is_refine; every `check_val_every_n_epoch` epochs a validation_step on the first frame and ONE step of

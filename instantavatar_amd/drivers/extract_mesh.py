@@ -37,7 +37,17 @@ the maximum and the mean distance, over all frames and vertices, between the rig
 "surface distance"; `Mesh.compare`): SAMPLES surface samples per direction (default 100 000), one `deviation:` line with the mean, the
 95th percentile and the maximum of the distances both ways in metres and in lattice spacings, and `deviation.json` with the whole
 report.  With --render it also writes `deviation_front.png`: the EXTRACTED mesh under the camera of `canonical_front.png`, every
-vertex coloured by its distance to the final mesh, blue (0) over green to red (2 lattice spacings and more)."""
+vertex coloured by its distance to the final mesh, blue (0) over green to red (2 lattice spacings and more).
+
+--photo (with --texture BLOCK) additionally textures the mesh from the frames of a sequence (DESIGN.md section 4, "photo texture";
+`AvatarModel.bake_photo_texture`): every frame's posed mesh is rasterised for its depth map and the frame's pixels are projected
+onto the texels that face its camera and are neither hidden nor outside the mask; texels that no frame saw keep the colour of the
+field-baked atlas.  The frames are the `train` split of --data DIR (with --dataset / --start / --end / --skip / --downscale as in
+the train driver), or with --synthetic --photo-frames N renderings of the synthetic subject at --photo-res^2 whose body turns
+through a full circle.  It writes `canonical_phototextured.obj` / `.mtl` / `.png` and `coverage.png` (the atlas layout, red: no
+frame saw the texel, over green to blue: the largest count), with --render `canonical_front_phototextured.png`; with --rig,
+`avatar.glb` carries the photo texture.  One line reports the frames used, the share of owned texels seen at least once, the
+median number of frames per seen texel and the wall time."""
 import argparse
 import os
 import sys
@@ -45,7 +55,7 @@ import time
 
 import numpy as np
 
-from . import animate
+from . import animate, sequence_args
 
 
 def main(argv=None):
@@ -76,12 +86,23 @@ def main(argv=None):
     ap.add_argument("--fps", type=float, default=30.0, help="--rig with --poses: key frames per second of the glTF animation")
     ap.add_argument("--deviation", type=int, nargs="?", const=100000, default=None, metavar="SAMPLES", help="with --smooth / --simplify: report the "
                     "distance between the extracted and the processed mesh from SAMPLES surface samples per direction (default 100000)")
+    ap.add_argument("--photo", action="store_true", help="--texture: also texture the mesh from the frames of --data DIR (or, with --synthetic, "
+                    "from generated frames): canonical_phototextured.{obj,mtl,png}, coverage.png")
+    ap.add_argument("--photo-frames", type=int, default=8, metavar="N", help="--photo --synthetic: the number of generated frames")
+    ap.add_argument("--photo-res", type=int, default=256, metavar="SIZE", help="--photo --synthetic: the edge of the generated frames in pixels")
+    sequence_args.add_data_arguments(ap)
     ap.add_argument("--out", default="meshes/out")
     args = ap.parse_args(argv)
     if args.deviation is not None and not (args.smooth or args.simplify):
         ap.error("--deviation compares the extracted mesh with the processed one: it needs --smooth or --simplify")
     if args.deviation is not None and args.deviation < 0:
         ap.error("--deviation %d: the number of samples cannot be negative" % args.deviation)
+    if args.photo and not args.texture:
+        ap.error("--photo textures the atlas of --texture BLOCK from the frames: it needs --texture")
+    if args.photo and not (args.synthetic or args.data):
+        ap.error("--photo needs a frame source: --data DIR, or --synthetic")
+    if args.photo and (args.photo_frames < 1 or args.photo_res < 8):
+        ap.error("--photo-frames must be at least 1 and --photo-res at least 8")
     if not args.synthetic and not args.ckpt:
         ap.error("--ckpt is required unless --synthetic is given")
     if args.smooth < 0:
@@ -166,6 +187,27 @@ def main(argv=None):
         print("texture: atlas %d x %d texels in blocks of %d, snap %.4g, %d of %d owned texels (%.2f %%) without a surface crossing (%.3f s, "
               "file writing included)" % (tex.size, tex.size, tex.block, snap, unsnapped, n_owned, 100.0 * unsnapped / max(n_owned, 1),
                                           time.perf_counter() - t0))
+    photo = None
+    if args.photo:
+        from PIL import Image
+        from .. import phototex
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if args.data:
+            from ..utils.sampler import EdgeSampler
+            frames = sequence_args.load_directory(args, "train", EdgeSampler(num_sample=4096, ratio_mask=0.6, ratio_edge=0.3, kernel_size=16), device)
+        else:
+            from . import eval as eval_driver
+            frames = eval_driver.synthetic_photo_set(device, model, args.photo_res, args.photo_frames)
+        photo, seen = model.bake_photo_texture(mesh, frames, block=args.texture, base=textured.texture)
+        owned = photo.texture.rgba8[..., 3] != 0
+        counts = seen[owned & (seen > 0)]
+        median = counts.sort().values[(counts.numel() - 1) // 2].long() if counts.numel() else torch.zeros((), dtype=torch.long, device=device)
+        n_owned, n_seen, median = torch.stack([owned.sum(), (owned & (seen > 0)).sum(), median]).tolist()     # the one host read
+        photo.to_obj_textured(os.path.join(args.out, "canonical_phototextured.obj"))
+        Image.fromarray(animate._bgra_to_rgba(phototex.coverage_image(seen, owned).cpu().numpy()), "RGBA").save(os.path.join(args.out, "coverage.png"))
+        print("photo texture: %d frames, %d of %d owned texels (%.2f %%) seen at least once, median %d frames per seen texel (%.3f s, frames and "
+              "file writing included)" % (len(frames), n_seen, n_owned, 100.0 * n_seen / max(n_owned, 1), median, time.perf_counter() - t0))
     if args.render:
         from PIL import Image
         from .. import mesh as mesh_mod, raster
@@ -175,6 +217,9 @@ def main(argv=None):
         if textured is not None:
             front = textured.render(cam)["rgba8"].cpu().numpy()
             Image.fromarray(animate._bgra_to_rgba(front), "RGBA").save(os.path.join(args.out, "canonical_front_textured.png"))
+        if photo is not None:
+            front = photo.render(cam)["rgba8"].cpu().numpy()
+            Image.fromarray(animate._bgra_to_rgba(front), "RGBA").save(os.path.join(args.out, "canonical_front_phototextured.png"))
     n = 0
     rig = model.rig_mesh(mesh, influences=args.rig) if args.rig else None
     animation = None
@@ -219,9 +264,9 @@ def main(argv=None):
             print("rig: %d influences per vertex deviate from the posed meshes by at most %.3e, %.3e on average over %d frames"
                   % (args.rig, float(dev_max), float(dev_sum) / n, n))
     if rig is not None:
-        (textured if textured is not None else mesh).to_glb(os.path.join(args.out, "avatar.glb"), rig, animation, args.fps)
+        (photo if photo is not None else textured if textured is not None else mesh).to_glb(os.path.join(args.out, "avatar.glb"), rig, animation, args.fps)
         print("rig: avatar.glb with %d vertices, 24 joints, %d influences%s%s" % (
-            mesh.verts.shape[0], args.rig, ", textured" if textured is not None else "", ", %d key frames at %g per second" % (n, args.fps) if n else ""))
+            mesh.verts.shape[0], args.rig, ", photo-textured" if photo is not None else ", textured" if textured is not None else "", ", %d key frames at %g per second" % (n, args.fps) if n else ""))
     print("wrote canonical.%s%s to %s" % (args.format, " and %d posed meshes" % n if n else "", args.out))
     return 0
 

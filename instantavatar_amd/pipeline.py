@@ -123,6 +123,44 @@ class AvatarModel(torch.nn.Module):
         out.texture = texture.bake(mesh, sample, block, snap, level, steps, chunk)
         return out
 
+    def bake_photo_texture(self, mesh, frames, camera=None, block=8, base="field", indices=None, snap=None, level=10.0, **options):
+        """`mesh` (canonical) textured from the frames of a sequence (`phototex.bake`; DESIGN.md section 4, "photo texture") ->
+        (a copy of the mesh with `.texture` set, seen [T,T] int32: the frames that saw every texel).  frames: a `DeviceFrames`;
+        camera: a `raster.Camera` (None: `frames.camera()`); indices: the frames to use (None: all).  Per frame the mesh is posed
+        with the frame's SMPL parameters (`pose_mesh`), rasterised for its depth map (`raster.rasterize`) and projected into the
+        frame's image under its mask.  The poses come from the model's `SMPL_param` tables when they are as long as the sequence
+        (they are what the field was trained against), else from `frames.smpl_params`.  base: "field": texels no frame saw keep
+        the colour of `bake_texture(mesh, block, snap, level)`; None: they stay zero; or a Texture / atlas of the same layout.
+        options: cos_min, power, depth_tol, min_frames, chunk_frames, chunk of `phototex.bake`."""
+        import copy
+        from . import _lib, phototex, raster
+        _lib.require_cuda(mesh.verts, mesh.faces, frames.images)
+        camera = frames.camera() if camera is None else camera
+        if isinstance(base, str):
+            if base != "field":
+                raise _lib.IAError("bake_photo_texture: base = %r: \"field\", None, a Texture or an atlas" % (base,))
+            base = self.bake_texture(mesh, block=block, snap=snap, level=level).texture
+        indices = range(len(frames)) if indices is None else [int(i) for i in indices]
+        table = getattr(self, "SMPL_param", None)
+        if table is not None and table.global_orient.weight.shape[0] != len(frames):
+            table = None
+        p = frames.smpl_params
+
+        def per_frame():
+            for i in indices:
+                if table is not None:
+                    batch = table(torch.full((1,), i, dtype=torch.long, device=frames.images.device))
+                    batch = {k: v.detach() for k, v in batch.items()}
+                else:
+                    batch = {"betas": p["betas"][0][None], "global_orient": p["global_orient"][i][None], "body_pose": p["body_pose"][i][None],
+                             "transl": p["transl"][i][None]}
+                posed = self.pose_mesh(mesh, batch)
+                depth = raster.rasterize(posed.verts, posed.faces, camera).depth
+                yield posed.verts, camera, frames.images[i], frames.masks[i], depth
+        out = copy.copy(mesh)                  # the tensors are shared, the input keeps its `texture`
+        out.texture, seen = phototex.bake(mesh, per_frame(), block=block, base=base, **options)
+        return out, seen
+
     def rig_mesh(self, mesh, influences=4):
         """The standard rig of `mesh` (canonical): per vertex the `influences` largest skinning weights of the deformer's weight
         volume and their joints, plus the skeleton's rest offsets, canonical rotations and inverse bind matrices (`rig.build` ->
