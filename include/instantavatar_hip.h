@@ -463,7 +463,9 @@ int ia_transform_rays_w2s(const float *rays_o, const float *rays_d,
  * ia_march_train_compact: raymarch_train + jitter (z = t + jitter*dt, jitter
  *   [n_rays,max_samples] as torch.rand_like draws it at :156, NULL = 0.5) + compaction:
  *   s_pts [cap,3], s_z [cap], s_slot [cap] (slot in the dense layout), ray_off/ray_cnt
- *   [n_rays], n_samples (device int32, zeroed inside).
+ *   [n_rays], n_samples (device int32, zeroed inside).  A ray with far <= near or a NaN bound takes
+ *   no sample (the reference loop `while (t < far)` is never entered); samples past sample_cap are
+ *   counted in n_samples but not written.
  * ia_composite_train_fwd: per sample max over its candidates (invalid = -1e5; cand_cap =
  *   length of the candidate arrays, candidates past it were dropped by the search),
  *   optional sigma noise (noise [n_rays,max_samples] as torch.randn_like draws it at :167:

@@ -1309,11 +1309,14 @@ __global__ __launch_bounds__(64 * IA_MT_RAYS) void k_march_train_compact(
     r.far = fars[n]; r.dt = dt;
     float t = t0;
     for (int k = 0; k < lane * spl; k++) t += dt;  // the sequential sum of the reference loop
+    // far < near: the reference loop is never entered (its first test fails), but with dt < 0 the running sum FALLS and a
+    // later lane's t would pass `t < far` -- a step belongs to the loop only while the sum rises
+    const bool fwd = dt > 0.f;
 #pragma unroll
     for (int q = 0; q < SPL_MAX; q++) {
       tk[q] = t;
       float x, y, z;
-      occf[q] = q < spl && t < r.far && march_occupied(r, bits, occ.G, t, x, y, z);
+      occf[q] = q < spl && fwd && t < r.far && march_occupied(r, bits, occ.G, t, x, y, z);
       c += occf[q] ? 1 : 0;
       t += dt;
     }
