@@ -1,0 +1,262 @@
+"""Scene composition: several rendered avatars, a ground plane that receives their shadows and a background in one frame
+(csrc/ia_scene.hip, include/instantavatar_hip_scene.h; definition in DESIGN.md section 4, "scene composition").
+
+    ground = scene.ground_under(models, seqs, cell=0.5)
+    sc = scene.Scene(models, seqs, ground=ground, light=(-2.0, -4.0, 2.0), jitter=animate.fixed_jitter(1, device))
+    out = sc.render(i)            # rgb [H,W,3], alpha, depth [H,W], rgba8 [H,W,4], shade [H,W], contested (device int32)
+
+Every avatar is rendered by `AvatarModel.render_image_fast` as it is, once for the camera; with a light and a ground it is rendered a
+second time from the light for its opacity, which is what no external compositing tool can get from the RGBA frames.  The layers are
+then ordered by depth per pixel and composited front to back (`composite`, a thin wrapper over the three entry points; no host read).
+
+Two limits, both stated in the header: a layer is a whole avatar, so the order is exact only where the avatars do not interleave
+along a ray (`contested` counts the pixels where they may); and only the ground receives shadows.  The scene renders eagerly:
+captured graphs, frames in flight and multi-rank sharding are the single-avatar drivers' and are not used here.
+
+Colours are in the model's channel order (the (B, G, R) order of the training images, see `drivers.animate.write_frames`)."""
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_LAYERS = 8      # IA_SCENE_MAX_LAYERS
+
+
+class Ground:
+    """The plane normal . x = offset; `normal` has unit length and points to the side objects stand on (in the drivers' camera +y
+    points down, so a floor has normal (0, -1, 0)).  color / color2: the two colours of a checker of edge `cell` metres (cell = 0 or
+    color2 = None: plain `color`), in the model's channel order.  The plane is a disc around `centre` (None: the point of the plane
+    nearest to the origin): opaque inside r0, fading linearly to nothing at r1."""
+
+    def __init__(self, normal=(0.0, -1.0, 0.0), offset=0.0, color=(0.8, 0.8, 0.8), color2=None, cell=0.0, centre=None, r0=3.0, r1=5.0):
+        n = np.asarray(normal, np.float64).reshape(3)
+        n = n / np.linalg.norm(n)
+        self.normal = tuple(float(v) for v in n)
+        self.offset = float(offset)
+        self.color = tuple(float(v) for v in color)
+        self.color2 = self.color if color2 is None else tuple(float(v) for v in color2)
+        self.cell = 0.0 if color2 is None else float(cell)
+        c = n * self.offset if centre is None else np.asarray(centre, np.float64).reshape(3)
+        self.centre = tuple(float(v) for v in c)
+        self.r0, self.r1 = float(r0), float(r1)
+        if not 0 <= self.r0 <= self.r1:
+            raise _lib.IAError("scene.Ground: the radii need 0 <= r0 <= r1, got %r, %r" % (r0, r1))
+
+
+def place(seq, offset):
+    """moves the avatar of an `AnimateSequence` by `offset` [3] metres: added to `transl` after the sequence has centred it"""
+    seq.transl = seq.transl + torch.as_tensor(np.asarray(offset, np.float32).reshape(1, 3), device=seq.transl.device)
+    return seq
+
+
+@torch.no_grad()
+def ground_under(models, seqs, **ground_options):
+    """A floor (normal (0, -1, 0): +y points down in the drivers' camera) through the lowest body-model vertex over all frames of all
+    avatars, i.e. at the largest y of `SMPL.forward`'s vertices, centred under the mean root translation.  models: one model or one
+    per sequence.  One host read (four floats)."""
+    if not isinstance(models, (list, tuple)):
+        models = [models] * len(seqs)
+    lows, roots = [], []
+    for model, seq in zip(models, seqs):
+        body = model.deformer.body_model
+        n = len(seq)
+        for f0 in range(0, n, 64):
+            th = seq.thetas[f0:f0 + 64]
+            out = body(betas=seq.betas.expand(th.shape[0], -1), body_pose=th[:, 3:], global_orient=th[:, :3], transl=seq.transl[f0:f0 + 64])
+            lows.append(out.vertices[..., 1].max().reshape(1))
+        roots.append(seq.transl.mean(0))
+    y, cx, _, cz = torch.cat([torch.cat(lows).max().reshape(1), torch.stack(roots).mean(0)]).cpu().tolist()
+    opts = dict(ground_options)
+    opts.setdefault("centre", (cx, y, cz))
+    return Ground(normal=(0.0, -1.0, 0.0), offset=-y, **opts)
+
+
+def light_camera(light_pos, target, extent=2.4, size=256, device="cuda", near=0.05):
+    """The `raster.Camera` of a point light at `light_pos` that looks at `target` (an avatar's root translation in that frame), built
+    on the host in fp64: z = (target - light) / |target - light|; the image's down direction is world +y (the drivers' down) unless z
+    is within 8 degrees of it (|z_y| > 0.99), then world +z; x = down x z normalised, y = z x x; w2c = [x; y; z | -R light].  The
+    focal length size |target - light| / extent makes `extent` metres at the target's distance fill the `size`^2 map; the
+    principal point is the map's centre (size - 1) / 2."""
+    from .raster import Camera
+    light, target = np.asarray(light_pos, np.float64).reshape(3), np.asarray(target, np.float64).reshape(3)
+    z = target - light
+    dist = float(np.linalg.norm(z))
+    if not dist > 0:
+        raise _lib.IAError("scene.light_camera: the light is at its target")
+    z = z / dist
+    down = np.array([0.0, 1.0, 0.0]) if abs(z[1]) <= 0.99 else np.array([0.0, 0.0, 1.0])
+    x = np.cross(down, z)
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    w2c = np.eye(4)
+    w2c[:3, :3] = np.stack([x, y, z])
+    w2c[:3, 3] = -w2c[:3, :3] @ light
+    f = size * dist / float(extent)
+    K = np.array([[f, 0.0, (size - 1) / 2.0], [0.0, f, (size - 1) / 2.0], [0.0, 0.0, 1.0]])
+    cam = Camera(K, torch.as_tensor(w2c, dtype=torch.float32, device=device), size, size, near=near)
+    cam.w2c_host = w2c
+    return cam
+
+
+def light_rays(cam):
+    """(rays_o, rays_d) [S*S,3] fp32 host arrays of a `light_camera`, exactly as `drivers.animate.make_rays` makes them from its K and
+    c2w, and its projection K [R | t] [3,4] fp32 (what `ia_scene_shadow` takes)"""
+    from .drivers.animate import make_rays
+    w2c = cam.w2c_host
+    c2w = np.linalg.inv(w2c)
+    o, d = make_rays(cam.K, c2w, cam.H, cam.W)
+    return o, d, (cam.K @ w2c[:3, :4]).astype(np.float32)
+
+
+@torch.no_grad()
+def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None, contact=0.3):
+    """layers: a list of 1 .. 8 (rgb [..,3], alpha [..], depth [..]) of `render_image_fast` with a zero `bg_color` in the batch --
+    premultiplied colour, opacity, depth SUM -- all over the same rays rays_o, rays_d [..,3].  ground: a `Ground`; shadows: (maps
+    [K,S,S] light-view opacity, cameras: K `light_camera`s or a [K,3,4] tensor of projections, PCF radius, strength), used with a
+    ground only; background: None, a colour of three numbers, a [3] tensor or an image [..,3] over the same pixels.
+    -> dict(rgb, alpha, depth, rgba8, shade, contested) shaped like the layers; `shade` is None without a ground, `contested` a
+    device int32 scalar.  Three launches at most, a pack and a zero-fill; no host read."""
+    K = len(layers)
+    if not 1 <= K <= MAX_LAYERS:
+        raise _lib.IAError("scene.composite: %d layers, 1 .. %d can be composited" % (K, MAX_LAYERS))
+    shape = tuple(layers[0][1].shape)
+    R = int(layers[0][1].numel())
+    dev = layers[0][1].device
+    for rgb, alpha, depth in layers:
+        _lib.require_cuda(rgb, alpha, depth)
+        if alpha.numel() != R or depth.numel() != R or rgb.numel() != 3 * R:
+            raise _lib.IAError("scene.composite: the layers do not cover the same pixels")
+    f = lambda t: t.detach().float()
+    c = torch.stack([f(l[0]).reshape(R, 3) for l in layers]).contiguous()
+    a = torch.stack([f(l[1]).reshape(R) for l in layers]).contiguous()
+    d = torch.stack([f(l[2]).reshape(R) for l in layers]).contiguous()
+    t_g = a_g = c_g = shade = None
+    if ground is not None:
+        o, dr = f(rays_o).reshape(-1, 3).contiguous(), f(rays_d).reshape(-1, 3).contiguous()
+        _lib.require_cuda(o, dr)
+        if o.shape[0] != R or dr.shape[0] != R:
+            raise _lib.IAError("scene.composite: %d rays for layers of %d pixels" % (o.shape[0], R))
+        t_g, a_g, c_g, P = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty((R, 3), device=dev), torch.empty((R, 3), device=dev)
+        _lib.call("ia_scene_ground", o, dr, R, *ground.normal, ground.offset, *ground.color, *ground.color2, ground.cell, *ground.centre,
+                  ground.r0, ground.r1, t_g, a_g, c_g, P)
+        if shadows is not None:
+            maps, cams, radius, strength = shadows
+            maps = f(maps).contiguous()
+            if torch.is_tensor(cams):
+                proj, near = f(cams).reshape(-1, 3, 4).contiguous(), 0.05
+            else:
+                proj = torch.as_tensor(np.stack([light_rays_projection(cm) for cm in cams]), device=dev)
+                near = min(cm.near for cm in cams)
+            if maps.dim() != 3 or maps.shape[1] != maps.shape[2] or maps.shape[0] != proj.shape[0]:
+                raise _lib.IAError("scene.composite: %s opacity maps for %d light cameras" % (tuple(maps.shape), proj.shape[0]))
+            shade = torch.empty(R, device=dev)
+            _lib.call("ia_scene_shadow", P, a_g, R, maps, proj, int(maps.shape[0]), int(maps.shape[1]), int(radius), float(strength), near, shade)
+        else:
+            shade = torch.ones(R, device=dev)
+    bg, bg_const = None, 0
+    if background is not None:
+        bg = background if torch.is_tensor(background) else torch.as_tensor(np.asarray(background, np.float32), device=dev)
+        bg = f(bg).contiguous()
+        _lib.require_cuda(bg)
+        if bg.numel() == 3:
+            bg_const = 1
+        elif bg.numel() != 3 * R:
+            raise _lib.IAError("scene.composite: a background of %d values for %d pixels" % (bg.numel(), R))
+    rgb, alpha, depth = torch.empty((R, 3), device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
+    contested = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.call("ia_scene_zero", contested, 1)
+    _lib.call("ia_scene_composite", c, a, d, K, R, t_g, a_g, c_g, shade, bg, bg_const, float(contact), rgb, alpha, depth, contested)
+    rgba8 = torch.empty((R, 4), dtype=torch.uint8, device=dev)
+    _lib.call("ia_pack_rgba8", rgb, alpha, R, rgba8)
+    return dict(rgb=rgb.reshape(*shape, 3), alpha=alpha.reshape(shape), depth=depth.reshape(shape), rgba8=rgba8.reshape(*shape, 4),
+                shade=None if shade is None else shade.reshape(shape), contested=contested.reshape(()))
+
+
+def light_rays_projection(cam):
+    """K [R | t] [3,4] fp32 of a camera: from the host copy a `light_camera` keeps, else from the device w2c (a host read)"""
+    w2c = getattr(cam, "w2c_host", None)
+    if w2c is None:
+        w2c = cam.w2c.double().cpu().numpy()
+    return (cam.K @ w2c[:3, :4]).astype(np.float32)
+
+
+class Scene:
+    """models, seqs: one `AvatarModel` and one `drivers.animate.AnimateSequence` per avatar (1 .. 8; the same model object may
+    appear twice), all sequences with the camera of the first -- every avatar shares its rays.  Avatars are placed with `place`.
+    ground: a `Ground`; light: the position [3] of a point light (shadows need both); shadow_size: the edge of the light-view
+    opacity maps, `extent` metres wide around every avatar's root; shadow_radius / shadow_strength: PCF radius 0 .. 3 and the
+    darkness of a full shadow; background: as `composite`; jitter: one occupancy-probe jitter for every render
+    (`drivers.animate.fixed_jitter`; without it the occupancy probes, and with them the bytes, are random); phases: per avatar,
+    frame i of the scene shows frame (i + phase) modulo the length of its sequence.
+
+    `render(i)`: per avatar one `render_image_fast` for the camera, with a zero `bg_color` so that the colour is premultiplied;
+    with a light and a ground one more render from the light through `_render`, which reuses the deformer and the test occupancy
+    grid the first render prepared for the frame (both depend on the pose alone, not on the rays) and of which only the opacity at
+    shadow_size^2 is kept; then `composite`.  `contested_total` (device int64) adds up the contested pixels over the calls."""
+
+    def __init__(self, models, seqs, ground=None, light=None, shadow_size=256, background=None, jitter=None, shadow_radius=1,
+                 shadow_strength=0.6, extent=2.4, contact=0.3, phases=None):
+        if not isinstance(models, (list, tuple)):
+            models = [models] * len(seqs)
+        if len(models) != len(seqs) or not 1 <= len(seqs) <= MAX_LAYERS:
+            raise _lib.IAError("scene.Scene: %d models for %d sequences; 1 .. %d avatars" % (len(models), len(seqs), MAX_LAYERS))
+        first = seqs[0]
+        for s in seqs:
+            if (s.H, s.W) != (first.H, first.W) or not np.array_equal(s.K, first.K):
+                raise _lib.IAError("scene.Scene: the sequences do not share one camera")
+        self.models, self.seqs = list(models), list(seqs)
+        self.ground, self.background, self.jitter = ground, background, jitter
+        self.light = None if light is None else np.asarray(light, np.float64).reshape(3)
+        self.shadow_size, self.shadow_radius, self.shadow_strength = int(shadow_size), int(shadow_radius), float(shadow_strength)
+        self.extent, self.contact = float(extent), float(contact)
+        self.phases = [0] * len(seqs) if phases is None else [int(p) for p in phases]
+        self.H, self.W = first.H, first.W
+        self.device = first.rays_o.device
+        self._zero_bg = torch.zeros((1, self.H * self.W, 3), device=self.device)
+        # the light cameras are built on the host: the root translations are read once, here
+        self._transl_host = [s.transl.double().cpu().numpy() for s in seqs] if self.shadows else None
+        self.contested_total = torch.zeros((), dtype=torch.int64, device=self.device)
+
+    @property
+    def shadows(self):
+        return self.light is not None and self.ground is not None
+
+    def __len__(self):
+        return max(len(s) for s in self.seqs)
+
+    @torch.no_grad()
+    def light_view(self, k, idx, batch):
+        """the opacity [S,S] of avatar k from the light and the light's camera; the frame must be prepared (right behind the
+        avatar's `render_image_fast`)"""
+        S = self.shadow_size
+        cam = light_camera(self.light, self._transl_host[k][idx], self.extent, S, device=self.device)
+        o, d, _ = light_rays(cam)
+        t = lambda x: torch.as_tensor(x, device=self.device)[None]
+        lb = {key: batch[key] for key in ("betas", "global_orient", "body_pose", "transl")}
+        ones = torch.ones((1, S * S), device=self.device)
+        dist = float(np.linalg.norm(self._transl_host[k][idx] - self.light))
+        lb.update(rays_o=t(o), rays_d=t(d), near=ones * (dist - 1), far=ones * (dist + 1))
+        out, _ = self.models[k]._render(lb, eval_mode=True)
+        return out["alpha_coarse"].reshape(S, S), cam
+
+    @torch.no_grad()
+    def render(self, i):
+        size = (self.H, self.W)
+        first = self.seqs[0]
+        layers, maps, cams = [], [], []
+        for k, (model, seq) in enumerate(zip(self.models, self.seqs)):
+            idx = (int(i) + self.phases[k]) % len(seq)
+            batch = seq.batch(idx)
+            batch["rays_o"], batch["rays_d"] = first.rays_o, first.rays_d
+            batch["bg_color"] = self._zero_bg
+            rgb, depth, alpha, _ = model.render_image_fast(batch, size, jitter=self.jitter)
+            layers.append((rgb[0], alpha[0], depth[0]))
+            if self.shadows:
+                m, cam = self.light_view(k, idx, batch)
+                maps.append(m)
+                cams.append(cam)
+        shadows = (torch.stack(maps), cams, self.shadow_radius, self.shadow_strength) if self.shadows else None
+        out = composite(layers, first.rays_o, first.rays_d, ground=self.ground, shadows=shadows, background=self.background,
+                        contact=self.contact)
+        self.contested_total += out["contested"]
+        return out
