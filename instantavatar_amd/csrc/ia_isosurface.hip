@@ -12,63 +12,20 @@
 //
 // One lane = one lattice point, z fastest: the point owns the (up to) 7 edges towards the other corners of the cell whose
 // origin it is, and the lane handles that cell as well, so the eight corner loads of neighbouring lanes coalesce and cell
-// order = point order.  Counts are turned into offsets by three launches: per-workgroup sums, one exclusive scan over the
-// workgroup sums, and the in-workgroup scan (wave shuffles + LDS) added back -- integer sums, so the order is fixed.
+// order = point order.  Counts are turned into offsets by the three launches of ia_scan.h, the first of them fused into the marking
+// pass (k_iso_mark has both counts of a point at hand); the face pieces of the component pass come from ia_mesh_dev.h.
 #include "ia_common.h"
+#include "ia_mesh_dev.h"
+#include "ia_scan.h"
 #include "ia_search_dev.h"
 #include "../../include/instantavatar_hip_mesh.h"
 #define IA_MT_QUAL static __device__ const
 #include "ia_mt_table.h"
 
-#define IA_ISO_THREADS 256
-#define IA_ISO_WAVES (IA_ISO_THREADS / 64)
+#define IA_ISO_THREADS IA_SCAN_THREADS
+#define IA_ISO_WAVES IA_SCAN_WAVES
 
 struct IsoBox { float lo[3], hi[3]; };
-
-// exclusive prefix sum of v over the workgroup (IA_ISO_THREADS lanes) and the workgroup's total; s_w: IA_ISO_WAVES ints
-__device__ __forceinline__ int iso_block_scan(int v, int *s_w, int &total) {
-  int wave_total;
-  const int x = ia_wave_excl_scan(v, wave_total);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();                       // (s_w may still be read from a previous scan)
-  if (ia_lane() == 0) s_w[wave] = wave_total;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < IA_ISO_WAVES; w++) {
-    if (w < wave) base += s_w[w];
-    total += s_w[w];
-  }
-  return base + x;
-}
-
-// exclusive scan, in place, of up to two arrays of workgroup sums (workgroup b of the launch takes array b); totals[b] = sum
-__global__ __launch_bounds__(1024) void k_scan_sums(int32_t *a0, int n0, int32_t *a1, int n1, int32_t *__restrict__ totals) {
-  __shared__ int s_w[16];
-  int32_t *a = blockIdx.x == 0 ? a0 : a1;
-  const int n = blockIdx.x == 0 ? n0 : n1;
-  const int wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < n ? a[i] : 0;
-    int wave_total;
-    const int x = ia_wave_excl_scan(v, wave_total);
-    if (ia_lane() == 0) s_w[wave] = wave_total;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-      if (w < wave) before += s_w[w];
-      total += s_w[w];
-    }
-    if (i < n) a[i] = carry + before + x;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // lattice
@@ -200,7 +157,7 @@ __global__ __launch_bounds__(IA_ISO_THREADS) void k_iso_vbase(const uint8_t *__r
   __shared__ int s_w[IA_ISO_WAVES];
   const long long p = (long long)blockIdx.x * IA_ISO_THREADS + threadIdx.x;
   int total;
-  const int x = iso_block_scan(p < n ? __popc((uint32_t)vmask[p]) : 0, s_w, total);
+  const int x = ia_block_excl_scan(p < n ? __popc((uint32_t)vmask[p]) : 0, s_w, total);
   if (p < n) vbase[p] = vsum[blockIdx.x] + x;
 }
 
@@ -243,7 +200,7 @@ __global__ __launch_bounds__(IA_ISO_THREADS) void k_iso_faces(const float *__res
   iso_cell(sigma, N, level, cap, p, n, c);
   const int nf = iso_cell_triangles(c);
   int total;
-  int at = fsum[blockIdx.x] + iso_block_scan(nf, s_w, total);   // (the scan's barriers also publish s_edge)
+  int at = fsum[blockIdx.x] + ia_block_excl_scan(nf, s_w, total);   // (the scan's barrier also publishes s_edge)
   if (nf == 0) return;
   for (int t = 0; t < 6; t++) {
     const int cs = iso_case(c.in, t);
@@ -294,7 +251,7 @@ extern "C" int ia_iso_count(const float *sigma, int N, float level, int cap, voi
   hipStream_t s = (hipStream_t)stream;
   const long long n = (long long)N * N * N;
   hipLaunchKernelGGL(k_iso_mark, dim3(W.blocks), dim3(IA_ISO_THREADS), 0, s, sigma, N, level, cap, W.vmask, W.vsum, W.fsum);
-  hipLaunchKernelGGL(k_scan_sums, dim3(2), dim3(1024), 0, s, W.vsum, W.blocks, W.fsum, W.blocks, counts);
+  ia_scan_sums(ScanSums{W.vsum, W.blocks, counts, nullptr}, ScanSums{W.fsum, W.blocks, counts + 1, nullptr}, s);
   hipLaunchKernelGGL(k_iso_vbase, dim3(W.blocks), dim3(IA_ISO_THREADS), 0, s, W.vmask, n, W.vsum, W.vbase);
   IA_LAUNCH_CHECK("k_iso_vbase");
   return IA_OK;
@@ -347,9 +304,8 @@ __device__ __forceinline__ void cc_union(int32_t *parent, int a, int b) {
 }
 
 __device__ __forceinline__ bool cc_face(const int32_t *__restrict__ faces, int f, int nv, int v[3]) {
-#pragma unroll
-  for (int e = 0; e < 3; e++) v[e] = faces[(size_t)f * 3 + e];
-  return (uint32_t)v[0] < (uint32_t)nv && (uint32_t)v[1] < (uint32_t)nv && (uint32_t)v[2] < (uint32_t)nv;   // others are ignored
+  ia_face_load(faces, f, v);
+  return ia_face_in_range(v, nv);   // others are ignored
 }
 
 __global__ __launch_bounds__(256) void k_cc_init(int32_t *__restrict__ parent, unsigned long long *__restrict__ area, int nv, CcHead *head) {
@@ -378,15 +334,10 @@ __global__ __launch_bounds__(256) void k_cc_area(const float *__restrict__ verts
   unsigned long long a = 0ull;
   if (ok) {
     root = cc_find(parent, v[0]);
-    double p[3][3];
-#pragma unroll
-    for (int e = 0; e < 3; e++)
-#pragma unroll
-      for (int d = 0; d < 3; d++) p[e][d] = (double)verts[(size_t)v[e] * 3 + d];
-    const double u0 = p[1][0] - p[0][0], u1 = p[1][1] - p[0][1], u2 = p[1][2] - p[0][2];
-    const double w0 = p[2][0] - p[0][0], w1 = p[2][1] - p[0][1], w2 = p[2][2] - p[0][2];
-    const double c0 = u1 * w2 - u2 * w1, c1 = u2 * w0 - u0 * w2, c2 = u0 * w1 - u1 * w0;
-    const double fixed = 0.5 * sqrt(c0 * c0 + c1 * c1 + c2 * c2) * scale;
+    double p[3][3], c[3];
+    ia_face_corners(verts, v, p);
+    ia_face_cross(p, c);
+    const double fixed = 0.5 * ia_len3d(c) * scale;
     a = fixed >= 1.0 && fixed < 4.0e18 ? (unsigned long long)fixed : 1ull;   // (tiny, NaN and overflowing areas count 1)
   }
   // most lanes of a wave belong to the same component: one atomic per wave then (integer sums: any order, the same total)
@@ -424,30 +375,13 @@ __device__ __forceinline__ bool cc_keep_vertex(int32_t *parent, int v, int nv, i
 __device__ __forceinline__ bool cc_keep_face(const int32_t *__restrict__ faces, const int32_t *__restrict__ vnew, int f, int nf, int nv, int v[3]) {
   return f < nf && cc_face(faces, f, nv, v) && vnew[v[0]] >= 0;
 }
-__device__ __forceinline__ int cc_block_count(bool flag, int *s_w) {
-  const int c = __popcll(__ballot(flag));
-  __syncthreads();
-  if (ia_lane() == 0) s_w[threadIdx.x >> 6] = c;
-  __syncthreads();
-  return s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-// index of a kept element among the kept elements of its workgroup (ballot + popcount inside the wave, LDS across waves)
-__device__ __forceinline__ int cc_block_rank(bool flag, int *s_w) {
-  const unsigned long long m = __ballot(flag);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (ia_lane() == 0) s_w[wave] = __popcll(m);
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) if (w < wave) base += s_w[w];
-  return base + __popcll(m & ((1ull << ia_lane()) - 1ull));
-}
+// (the index of a kept element among the kept elements of its workgroup, and their number: ia_block_rank)
 
 __global__ __launch_bounds__(256) void k_cc_count_verts(int32_t *parent, int nv, const CcHead *__restrict__ head, int32_t *__restrict__ vsum) {
   __shared__ int s_w[4];
   const int v = blockIdx.x * 256 + threadIdx.x;
-  const int c = cc_block_count(cc_keep_vertex(parent, v, nv, head->best_root), s_w);
+  int c;
+  ia_block_rank(cc_keep_vertex(parent, v, nv, head->best_root), s_w, c);
   if (threadIdx.x == 0) vsum[blockIdx.x] = c;
 }
 __global__ __launch_bounds__(256) void k_cc_index_verts(int32_t *parent, int nv, const CcHead *__restrict__ head, const int32_t *__restrict__ vsum,
@@ -455,15 +389,16 @@ __global__ __launch_bounds__(256) void k_cc_index_verts(int32_t *parent, int nv,
   __shared__ int s_w[4];
   const int v = blockIdx.x * 256 + threadIdx.x;
   const bool keep = cc_keep_vertex(parent, v, nv, head->best_root);
-  const int r = cc_block_rank(keep, s_w);
+  int c;
+  const int r = ia_block_rank(keep, s_w, c);
   if (v < nv) vnew[v] = keep ? vsum[blockIdx.x] + r : -1;
 }
 __global__ __launch_bounds__(256) void k_cc_count_faces(const int32_t *__restrict__ faces, int nf, int nv, const int32_t *__restrict__ vnew,
                                                         int32_t *__restrict__ fsum) {
   __shared__ int s_w[4];
   const int f = blockIdx.x * 256 + threadIdx.x;
-  int v[3];
-  const int c = cc_block_count(cc_keep_face(faces, vnew, f, nf, nv, v), s_w);
+  int v[3], c;
+  ia_block_rank(cc_keep_face(faces, vnew, f, nf, nv, v), s_w, c);
   if (threadIdx.x == 0) fsum[blockIdx.x] = c;
 }
 
@@ -481,9 +416,9 @@ __global__ __launch_bounds__(256) void k_cc_emit_faces(const int32_t *__restrict
                                                        const int32_t *__restrict__ fsum, int32_t *__restrict__ faces_out, int cap) {
   __shared__ int s_w[4];
   const int f = blockIdx.x * 256 + threadIdx.x;
-  int v[3];
+  int v[3], c;
   const bool keep = cc_keep_face(faces, vnew, f, nf, nv, v);
-  const int k = fsum[blockIdx.x] + cc_block_rank(keep, s_w);
+  const int k = fsum[blockIdx.x] + ia_block_rank(keep, s_w, c);
   if (!keep || (uint32_t)k >= (uint32_t)cap) return;
 #pragma unroll
   for (int e = 0; e < 3; e++) faces_out[(size_t)k * 3 + e] = vnew[v[e]];
@@ -528,10 +463,10 @@ extern "C" int ia_mesh_largest_count(const float *verts, const int32_t *faces, i
   }
   // (without a face nothing is kept: best_root stays INT_MAX)
   hipLaunchKernelGGL(k_cc_count_verts, gv, b, 0, s, W.parent, nv, W.head, W.vsum);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, s, W.vsum, W.vblocks, (int32_t *)nullptr, 0, counts);
+  ia_scan_sums(ScanSums{W.vsum, W.vblocks, counts, nullptr}, s);
   hipLaunchKernelGGL(k_cc_index_verts, gv, b, 0, s, W.parent, nv, W.head, W.vsum, W.vnew);
   hipLaunchKernelGGL(k_cc_count_faces, gf, b, 0, s, faces, nf, nv, W.vnew, W.fsum);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, s, W.fsum, W.fblocks, (int32_t *)nullptr, 0, counts + 1);
+  ia_scan_sums(ScanSums{W.fsum, W.fblocks, counts + 1, nullptr}, s);
   IA_LAUNCH_CHECK("k_cc_count_faces");
   return IA_OK;
 }

@@ -10,74 +10,51 @@
 // Why the result does not depend on the grid.  A point's result is the minimum of (d2, face) over every face the walk evaluates, d2
 // being one fixed fp64 expression of the point and the face's corners; the walk may only stop when every face it has not evaluated
 // has d2 > the best.  A face is listed in the block of cells [cell(min corner), cell(max corner)] per axis, with the fp32 cell
-// function of the cluster grid, which is monotone in the coordinate.  After shell r the visited cells are the block [c - r, c + r]
+// function of ia_mesh_dev.h (ia_grid_cell), which is monotone in the coordinate.  After shell r the visited cells are the block [c - r, c + r]
 // (clamped); a face listed nowhere in it has, on some axis a, cell(min_a) >= c_a + r + 1 or cell(max_a) <= c_a - r - 1.  The fp32
 // value t = fl(fl(x - lo) inv_h) differs from (x - lo) / h by a factor within (1 +- 2^-24)^3, so in the first case every coordinate of
 // the face is >= lo + (c_a + r + 1)(1 - 2^-22) h and in the second <= lo + (c_a - r)(1 + 2^-22) h: the distance of the point's own
 // coordinate to that plane bounds its distance to the face from below, wherever the point and the face lie relative to the box.  The
 // smallest such distance over the sides of the block that are not flush with the grid's boundary (negative ones count as 0) bounds
 // everything unvisited.  The argument never uses that c is the point's geometric cell, only that the shells are centred on it.
+// The grid, its cell function and the face pieces are ia_mesh_dev.h's; the scan of the cells' counts and the fill are ia_scan.h's.
 #include "ia_common.h"
+#include "ia_mesh_dev.h"
+#include "ia_scan.h"
 #include "../../include/instantavatar_hip_meshdist.h"
 
-#define IA_MD_THREADS 256
-#define IA_MD_WAVES (IA_MD_THREADS / 64)
+#define IA_MD_THREADS IA_SCAN_THREADS
 
 namespace {
-
-inline int md_blocks(long long n) { return (int)((n + IA_MD_THREADS - 1) / IA_MD_THREADS); }
-
-struct MdGrid { float lo[3]; float h, inv_h; int n[3]; };
-
-// cell of a coordinate along one axis (the cluster grid's formula): the clamp is taken on the float, NaN goes to 0
-__device__ __forceinline__ int md_cell(float p, float lo, float inv_h, int n) {
-  const float t = floorf((p - lo) * inv_h);
-  if (!(t > 0.f)) return 0;
-  if (t >= (float)(n - 1)) return n - 1;
-  return (int)t;
-}
-
-__device__ __forceinline__ bool md_finite(float x) { return __builtin_fabsf(x) < INFINITY; }
 
 // the corners of face f when it is valid: indices in [0, nv), pairwise different, finite corners, n = (p1 - p0) x (p2 - p0) finite and
 // not zero in fp64.  n is returned as well.
 __device__ __forceinline__ bool md_face(const float *__restrict__ verts, const int32_t *__restrict__ faces, int f, int nv, float p[3][3],
                                         double n[3]) {
   int v[3];
-#pragma unroll
-  for (int e = 0; e < 3; e++) v[e] = faces[(size_t)f * 3 + e];
-  if ((uint32_t)v[0] >= (uint32_t)nv || (uint32_t)v[1] >= (uint32_t)nv || (uint32_t)v[2] >= (uint32_t)nv) return false;
-  if (v[0] == v[1] || v[1] == v[2] || v[0] == v[2]) return false;
-  bool fin = true;
-#pragma unroll
-  for (int e = 0; e < 3; e++)
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      p[e][d] = verts[(size_t)v[e] * 3 + d];
-      fin = fin && md_finite(p[e][d]);
-    }
-  if (!fin) return false;
-  const double u0 = (double)p[1][0] - (double)p[0][0], u1 = (double)p[1][1] - (double)p[0][1], u2 = (double)p[1][2] - (double)p[0][2];
-  const double w0 = (double)p[2][0] - (double)p[0][0], w1 = (double)p[2][1] - (double)p[0][1], w2 = (double)p[2][2] - (double)p[0][2];
-  n[0] = u1 * w2 - u2 * w1; n[1] = u2 * w0 - u0 * w2; n[2] = u0 * w1 - u1 * w0;
-  if (!(fabs(n[0]) < (double)INFINITY && fabs(n[1]) < (double)INFINITY && fabs(n[2]) < (double)INFINITY)) return false;
+  ia_face_load(faces, f, v);
+  if (!ia_face_in_range(v, nv) || !ia_face_distinct(v)) return false;
+  ia_face_corners(verts, v, p);
+  if (!ia_corners_finite(p)) return false;
+  ia_face_cross(p, n);
+  if (!ia_finite3(n[0], n[1], n[2])) return false;
   return n[0] != 0.0 || n[1] != 0.0 || n[2] != 0.0;
 }
 
 // the block of cells of a face: per axis [cell(min corner), cell(max corner)]
-__device__ __forceinline__ void md_range(const MdGrid &G, const float p[3][3], int c0[3], int c1[3]) {
+__device__ __forceinline__ void md_range(const IaGrid &G, const float p[3][3], int c0[3], int c1[3]) {
 #pragma unroll
   for (int d = 0; d < 3; d++) {
     const float a = fminf(p[0][d], fminf(p[1][d], p[2][d])), b = fmaxf(p[0][d], fmaxf(p[1][d], p[2][d]));
-    c0[d] = md_cell(a, G.lo[d], G.inv_h, G.n[d]);
-    c1[d] = md_cell(b, G.lo[d], G.inv_h, G.n[d]);
+    c0[d] = ia_grid_cell(a, G.lo[d], G.inv_h, G.n[d]);
+    c1[d] = ia_grid_cell(b, G.lo[d], G.inv_h, G.n[d]);
   }
 }
 
 __global__ __launch_bounds__(IA_MD_THREADS) void k_md_zero64(unsigned long long *p) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = 0ull; }
 
 __global__ __launch_bounds__(IA_MD_THREADS) void k_md_count(const float *__restrict__ verts, const int32_t *__restrict__ faces, int nv, int nf,
-                                                            MdGrid G, unsigned long long *total) {
+                                                            IaGrid G, unsigned long long *total) {
   const long long f = (long long)blockIdx.x * IA_MD_THREADS + threadIdx.x;
   unsigned long long mine = 0ull;
   if (f < nf) {
@@ -94,15 +71,10 @@ __global__ __launch_bounds__(IA_MD_THREADS) void k_md_count(const float *__restr
   if (ia_lane() == 0 && mine) atomicAdd(total, mine);
 }
 
-__global__ __launch_bounds__(IA_MD_THREADS) void k_md_fill_i32(int32_t *__restrict__ p, long long n, int32_t value) {
-  const long long i = (long long)blockIdx.x * IA_MD_THREADS + threadIdx.x;
-  if (i < n) p[i] = value;
-}
-
 // pass 0: the face's record (three corners, or NaN for a face that is not valid) and the cells' counts; pass 1: the lists, through a
 // cursor per cell.  A slot at or past n_pairs is not written (the caller's count was of another input).
 __global__ __launch_bounds__(IA_MD_THREADS) void k_md_emit(const float *__restrict__ verts, const int32_t *__restrict__ faces, int nv, int nf,
-                                                           MdGrid G, int pass, float4 *__restrict__ tri, int32_t *cnt,
+                                                           IaGrid G, int pass, float4 *__restrict__ tri, int32_t *cnt,
                                                            const int32_t *__restrict__ start, int32_t *__restrict__ pairs, long long n_pairs) {
   const long long f = (long long)blockIdx.x * IA_MD_THREADS + threadIdx.x;
   if (f >= nf) return;
@@ -130,63 +102,6 @@ __global__ __launch_bounds__(IA_MD_THREADS) void k_md_emit(const float *__restri
       }
 }
 
-// exclusive scan of cnt [n] into start [n + 1] (integer sums: the order is fixed): per-workgroup sums, one scan over them, the
-// in-workgroup scan added back, as in ia_meshops.hip
-__global__ __launch_bounds__(IA_MD_THREADS) void k_md_block_sums(const int32_t *__restrict__ cnt, long long n, int32_t *__restrict__ bsum) {
-  __shared__ int s_w[IA_MD_WAVES];
-  const long long i = (long long)blockIdx.x * IA_MD_THREADS + threadIdx.x;
-  int v = i < n ? cnt[i] : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (ia_lane() == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = 0;
-#pragma unroll
-    for (int w = 0; w < IA_MD_WAVES; w++) a += s_w[w];
-    bsum[blockIdx.x] = a;
-  }
-}
-__global__ __launch_bounds__(1024) void k_md_scan_sums(int32_t *a, int n, int32_t *__restrict__ total) {
-  __shared__ int s_w[16];
-  const int wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < n ? a[i] : 0;
-    int wave_total;
-    const int x = ia_wave_excl_scan(v, wave_total);
-    if (ia_lane() == 0) s_w[wave] = wave_total;
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-      if (w < wave) before += s_w[w];
-      sum += s_w[w];
-    }
-    if (i < n) a[i] = carry + before + x;
-    carry += sum;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-__global__ __launch_bounds__(IA_MD_THREADS) void k_md_block_scan(const int32_t *__restrict__ cnt, long long n, const int32_t *__restrict__ bsum,
-                                                                 int32_t *__restrict__ start) {
-  __shared__ int s_w[IA_MD_WAVES];
-  const long long i = (long long)blockIdx.x * IA_MD_THREADS + threadIdx.x;
-  const int v = i < n ? cnt[i] : 0;
-  int wave_total;
-  const int x = ia_wave_excl_scan(v, wave_total);
-  const int wave = threadIdx.x >> 6;
-  if (ia_lane() == 0) s_w[wave] = wave_total;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < IA_MD_WAVES; w++)
-    if (w < wave) base += s_w[w];
-  if (i < n) start[i] = bsum[blockIdx.x] + base + x;
-}
-
 struct MdWs { float4 *tri; int32_t *start, *cnt, *bsum, *pairs; size_t bytes; };
 MdWs md_carve(void *ws, int nf, long long cells, long long n_pairs) {
   WsCarver w(ws, 0);
@@ -195,44 +110,24 @@ MdWs md_carve(void *ws, int nf, long long cells, long long n_pairs) {
   o.tri = w.take<float4>(3 * f);
   o.start = w.take<int32_t>(c + 1);
   o.cnt = w.take<int32_t>(c);
-  o.bsum = w.take<int32_t>((size_t)md_blocks((long long)c) + 1);
+  o.bsum = w.take<int32_t>((size_t)ia_div_up((long long)c, IA_MD_THREADS) + 1);
   o.pairs = w.take<int32_t>((size_t)(n_pairs > 0 ? n_pairs : 1));
   o.bytes = w.off;
   return o;
 }
 
-// the box, the cell edge and the sizes, checked; the grid and its number of cells
-int md_check(const char *who, int nf, const float lo[3], const float hi[3], float h, float inv_h, MdGrid *G, long long *cells) {
+// the size, the box and the cell edge, checked; the grid and its number of cells
+static_assert(IA_MESHDIST_MAX_CELLS == 16777216ll, "the text below");
+int md_check(const char *who, int nf, const float lo[3], const float hi[3], float h, float inv_h, IaGrid *G, long long *cells) {
   IA_CHECK_ARG(nf >= 0, "%s: nf = %d < 0", who, nf);
   IA_CHECK_ARG(nf <= IA_MESHDIST_MAX_FACES, "%s: nf = %d above %d", who, nf, IA_MESHDIST_MAX_FACES);
-  IA_CHECK_ARG(h > 0.f && h < INFINITY, "%s: the cell edge h = %g must be positive and finite", who, (double)h);
-  IA_CHECK_ARG(inv_h == (float)(1.0 / (double)h) && inv_h > 0.f && inv_h < INFINITY, "%s: inv_h = %g is not fp32(1 / h) = %g, positive and finite", who,
-               (double)inv_h, 1.0 / (double)h);
-  double total = 1.0;
-  for (int d = 0; d < 3; d++) {
-    IA_CHECK_ARG(fabsf(lo[d]) < INFINITY && fabsf(hi[d]) < INFINITY, "%s: the box is not finite", who);
-    double n = ceil(((double)hi[d] - (double)lo[d]) / (double)h);
-    if (!(n >= 1.0)) n = 1.0;
-    IA_CHECK_ARG(n <= (double)IA_MESHDIST_MAX_CELLS, "%s: a grid of more than %lld cells (axis %d alone has %.0f): enlarge h", who,
-                 IA_MESHDIST_MAX_CELLS, d, n);
-    G->lo[d] = lo[d];
-    G->n[d] = (int)n;
-    total *= n;
-  }
-  IA_CHECK_ARG(total <= (double)IA_MESHDIST_MAX_CELLS, "%s: a grid of %d x %d x %d cells is more than %lld: enlarge h", who, G->n[0], G->n[1],
-               G->n[2], IA_MESHDIST_MAX_CELLS);
-  G->h = h;
-  G->inv_h = inv_h;
-  *cells = (long long)G->n[0] * G->n[1] * G->n[2];
-  return IA_OK;
+  return ia_grid_check(who, lo, hi, h, inv_h, true, IA_MESHDIST_MAX_CELLS, "16777216", G, cells);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // closest point of one triangle (Ericson 5.1.5), fp64, no contraction (the build has -ffp-contract=off)
 // ---------------------------------------------------------------------------------------------------------------------
 struct MdHit { double d2, u, v, w, c[3]; };
-
-__device__ __forceinline__ double md_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 __device__ __forceinline__ void md_point_triangle(const double p[3], const double a[3], const double b[3], const double c[3], MdHit &o) {
   double ab[3], ac[3], ap[3], bp[3], cp[3];
@@ -241,9 +136,9 @@ __device__ __forceinline__ void md_point_triangle(const double p[3], const doubl
     ab[d] = b[d] - a[d]; ac[d] = c[d] - a[d];
     ap[d] = p[d] - a[d]; bp[d] = p[d] - b[d]; cp[d] = p[d] - c[d];
   }
-  const double d1 = md_dot(ab, ap), d2 = md_dot(ac, ap);
-  const double d3 = md_dot(ab, bp), d4 = md_dot(ac, bp);
-  const double d5 = md_dot(ab, cp), d6 = md_dot(ac, cp);
+  const double d1 = ia_dot3d(ab, ap), d2 = ia_dot3d(ac, ap);
+  const double d3 = ia_dot3d(ab, bp), d4 = ia_dot3d(ac, bp);
+  const double d5 = ia_dot3d(ab, cp), d6 = ia_dot3d(ac, cp);
   const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
   double u, v, w;
   if (d1 <= 0.0 && d2 <= 0.0) { u = 1.0; v = 0.0; w = 0.0; }                                  // vertex p0
@@ -290,7 +185,7 @@ __device__ __forceinline__ void md_visit(long long key, const double p[3], const
   }
 }
 
-__global__ __launch_bounds__(IA_MD_THREADS) void k_md_closest(const float *__restrict__ points, int P, int nf, MdGrid G, long long n_pairs,
+__global__ __launch_bounds__(IA_MD_THREADS) void k_md_closest(const float *__restrict__ points, int P, int nf, IaGrid G, long long n_pairs,
                                                               const float4 *__restrict__ tri, const int32_t *__restrict__ start,
                                                               const int32_t *__restrict__ pairs, float *__restrict__ dist,
                                                               int32_t *__restrict__ face, float *__restrict__ bary, float *__restrict__ closest,
@@ -300,14 +195,14 @@ __global__ __launch_bounds__(IA_MD_THREADS) void k_md_closest(const float *__res
   const float pf[3] = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
   MdBest B;
   B.d2 = (double)INFINITY; B.u = B.v = B.w = 0.0; B.face = -1; B.tests = 0;
-  const bool fin = md_finite(pf[0]) && md_finite(pf[1]) && md_finite(pf[2]);
+  const bool fin = ia_finite3(pf[0], pf[1], pf[2]);
   if (fin) {
     const double p[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
     int c[3];
     int rmax = 0;
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-      c[d] = md_cell(pf[d], G.lo[d], G.inv_h, G.n[d]);
+      c[d] = ia_grid_cell(pf[d], G.lo[d], G.inv_h, G.n[d]);
       const int far = c[d] > G.n[d] - 1 - c[d] ? c[d] : G.n[d] - 1 - c[d];
       rmax = far > rmax ? far : rmax;
     }
@@ -411,7 +306,7 @@ extern "C" size_t ia_meshdist_grid_workspace_bytes(int nf, long long n_cells, lo
 extern "C" int ia_meshdist_grid_count(const float *verts, const int32_t *faces, int nv, int nf, float lo_x, float lo_y, float lo_z, float hi_x,
                                       float hi_y, float hi_z, float h, float inv_h, long long *n_pairs, void *stream) {
   const float lo[3] = {lo_x, lo_y, lo_z}, hi[3] = {hi_x, hi_y, hi_z};
-  MdGrid G;
+  IaGrid G;
   long long cells;
   const int rc = md_check("ia_meshdist_grid_count", nf, lo, hi, h, inv_h, &G, &cells);
   if (rc) return rc;
@@ -420,7 +315,7 @@ extern "C" int ia_meshdist_grid_count(const float *verts, const int32_t *faces, 
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_md_zero64, dim3(1), dim3(IA_MD_THREADS), 0, s, reinterpret_cast<unsigned long long *>(n_pairs));
   if (nf > 0)
-    hipLaunchKernelGGL(k_md_count, dim3(md_blocks(nf)), dim3(IA_MD_THREADS), 0, s, verts, faces, nv, nf, G,
+    hipLaunchKernelGGL(k_md_count, dim3(ia_div_up(nf, IA_MD_THREADS)), dim3(IA_MD_THREADS), 0, s, verts, faces, nv, nf, G,
                        reinterpret_cast<unsigned long long *>(n_pairs));
   IA_LAUNCH_CHECK("k_md_count");
   return IA_OK;
@@ -429,7 +324,7 @@ extern "C" int ia_meshdist_grid_count(const float *verts, const int32_t *faces, 
 extern "C" int ia_meshdist_grid_build(const float *verts, const int32_t *faces, int nv, int nf, float lo_x, float lo_y, float lo_z, float hi_x,
                                       float hi_y, float hi_z, float h, float inv_h, long long n_pairs, void *ws, size_t ws_bytes, void *stream) {
   const float lo[3] = {lo_x, lo_y, lo_z}, hi[3] = {hi_x, hi_y, hi_z};
-  MdGrid G;
+  IaGrid G;
   long long cells;
   const int rc = md_check("ia_meshdist_grid_build", nf, lo, hi, h, inv_h, &G, &cells);
   if (rc) return rc;
@@ -440,16 +335,14 @@ extern "C" int ia_meshdist_grid_build(const float *verts, const int32_t *faces, 
   const MdWs W = md_carve(ws, nf, cells, n_pairs);
   if (ws_bytes < W.bytes) return ia_set_error(IA_ERR_WORKSPACE, "ia_meshdist_grid_build: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const dim3 b(IA_MD_THREADS), gc(md_blocks(cells));
-  hipLaunchKernelGGL(k_md_fill_i32, gc, b, 0, s, W.cnt, cells, 0);
+  const dim3 b(IA_MD_THREADS);
+  ia_fill_i32(W.cnt, cells, 0, s);
   if (nf > 0)
-    hipLaunchKernelGGL(k_md_emit, dim3(md_blocks(nf)), b, 0, s, verts, faces, nv, nf, G, 0, W.tri, W.cnt, (const int32_t *)W.start, W.pairs, n_pairs);
-  hipLaunchKernelGGL(k_md_block_sums, gc, b, 0, s, (const int32_t *)W.cnt, cells, W.bsum);
-  hipLaunchKernelGGL(k_md_scan_sums, dim3(1), dim3(1024), 0, s, W.bsum, md_blocks(cells), W.start + cells);
-  hipLaunchKernelGGL(k_md_block_scan, gc, b, 0, s, (const int32_t *)W.cnt, cells, (const int32_t *)W.bsum, W.start);
-  hipLaunchKernelGGL(k_md_fill_i32, gc, b, 0, s, W.cnt, cells, 0);
+    hipLaunchKernelGGL(k_md_emit, dim3(ia_div_up(nf, IA_MD_THREADS)), b, 0, s, verts, faces, nv, nf, G, 0, W.tri, W.cnt, (const int32_t *)W.start, W.pairs, n_pairs);
+  ia_scan(LoadInt{W.cnt}, cells, W.bsum, W.start, nullptr, s);
+  ia_fill_i32(W.cnt, cells, 0, s);
   if (nf > 0)
-    hipLaunchKernelGGL(k_md_emit, dim3(md_blocks(nf)), b, 0, s, verts, faces, nv, nf, G, 1, W.tri, W.cnt, (const int32_t *)W.start, W.pairs, n_pairs);
+    hipLaunchKernelGGL(k_md_emit, dim3(ia_div_up(nf, IA_MD_THREADS)), b, 0, s, verts, faces, nv, nf, G, 1, W.tri, W.cnt, (const int32_t *)W.start, W.pairs, n_pairs);
   IA_LAUNCH_CHECK("k_md_emit");
   return IA_OK;
 }
@@ -458,7 +351,7 @@ extern "C" int ia_meshdist_closest(const float *points, int P, int nf, float lo_
                                    float h, float inv_h, long long n_pairs, const void *ws, size_t ws_bytes, float *dist, int32_t *face,
                                    float *bary, float *closest, int32_t *tests, void *stream) {
   const float lo[3] = {lo_x, lo_y, lo_z}, hi[3] = {hi_x, hi_y, hi_z};
-  MdGrid G;
+  IaGrid G;
   long long cells;
   const int rc = md_check("ia_meshdist_closest", nf, lo, hi, h, inv_h, &G, &cells);
   if (rc) return rc;
@@ -469,7 +362,7 @@ extern "C" int ia_meshdist_closest(const float *points, int P, int nf, float lo_
   IA_CHECK_ARG(points && dist && ws, "ia_meshdist_closest: null pointer");
   const MdWs W = md_carve(const_cast<void *>(ws), nf, cells, n_pairs);
   if (ws_bytes < W.bytes) return ia_set_error(IA_ERR_WORKSPACE, "ia_meshdist_closest: workspace too small");
-  hipLaunchKernelGGL(k_md_closest, dim3(md_blocks(P)), dim3(IA_MD_THREADS), 0, (hipStream_t)stream, points, P, nf, G, n_pairs,
+  hipLaunchKernelGGL(k_md_closest, dim3(ia_div_up(P, IA_MD_THREADS)), dim3(IA_MD_THREADS), 0, (hipStream_t)stream, points, P, nf, G, n_pairs,
                      (const float4 *)W.tri, (const int32_t *)W.start, (const int32_t *)W.pairs, dist, face, bary, closest, tests);
   IA_LAUNCH_CHECK("k_md_closest");
   return IA_OK;
@@ -481,7 +374,7 @@ extern "C" int ia_meshdist_sample(const float *verts, const int32_t *faces, int 
   if (n == 0) return IA_OK;
   IA_CHECK_ARG(nf >= 1 && nv >= 1, "ia_meshdist_sample: %d samples of a mesh without faces", n);
   IA_CHECK_ARG(verts && faces && cum && points && face && bary, "ia_meshdist_sample: null pointer");
-  hipLaunchKernelGGL(k_md_sample, dim3(md_blocks(n)), dim3(IA_MD_THREADS), 0, (hipStream_t)stream, verts, faces, nv, nf, cum, n, points, face, bary);
+  hipLaunchKernelGGL(k_md_sample, dim3(ia_div_up(n, IA_MD_THREADS)), dim3(IA_MD_THREADS), 0, (hipStream_t)stream, verts, faces, nv, nf, cum, n, points, face, bary);
   IA_LAUNCH_CHECK("k_md_sample");
   return IA_OK;
 }

@@ -10,115 +10,22 @@
 //
 // All three operations need "for every key, its values in ascending order" (per cluster the face corners and the members, per
 // vertex the faces and the neighbours).  seg_build makes it: count per key with integer atomics, exclusive scan, fill through a
-// per-key cursor (any order), then every segment is sorted in place -- so what is read afterwards does not depend on the order
-// the atomics were served in.  Every floating-point sum is then taken by ONE lane walking ONE sorted segment, in fp64.
+// per-key cursor (any order), then every segment is sorted in place -- so what is read afterwards does not depend on the
+// order the atomics were served in.  Every floating-point sum is then taken by ONE lane walking ONE sorted segment, in fp64.
 // A vertex's lists are short (valence ~6): one lane sorts each.  A cell of 4^3 lattice cells holds a few hundred corners: one
 // wave ranks such a segment in LDS.  The hub of a fan or a very coarse cell can pass the LDS buffer: that segment is sorted by
 // one lane's in-place heapsort and, like every segment, summed by a single lane: slow, not wrong, no fixed-size per-thread array.
+// The scan and the fill are ia_scan.h's; the face pieces and the grid of cells are ia_mesh_dev.h's.
 #include "ia_common.h"
+#include "ia_mesh_dev.h"
+#include "ia_scan.h"
 #include "../../include/instantavatar_hip_meshops.h"
 
-#define IA_MO_THREADS 256
-#define IA_MO_WAVES (IA_MO_THREADS / 64)
+#define IA_MO_THREADS IA_SCAN_THREADS
 #define IA_MO_SORT_SHORT 16      // segments up to here: one lane each, insertion sort
 #define IA_MO_SORT_LDS 2048      // segments up to here: one wave each, ranked in LDS (16 KB); beyond: one lane, heapsort
 
 namespace {
-
-inline int mo_blocks(long long n) { return (int)((n + IA_MO_THREADS - 1) / IA_MO_THREADS); }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// exclusive prefix sums of a count per element (integer sums: the order is fixed), three launches as in ia_isosurface.hip:
-// per-workgroup sums, one scan over them, the in-workgroup scan added back.  start [n + 1], start[n] = the total.
-// ---------------------------------------------------------------------------------------------------------------------
-struct LoadInt {
-  const int32_t *p;
-  __device__ __forceinline__ int operator()(long long i) const { return p[i]; }
-};
-struct LoadPopc {
-  const uint32_t *p;
-  __device__ __forceinline__ int operator()(long long i) const { return __popc(p[i]); }
-};
-
-template <class L>
-__global__ __launch_bounds__(IA_MO_THREADS) void k_mo_block_sums(L load, long long n, int32_t *__restrict__ bsum) {
-  __shared__ int s_w[IA_MO_WAVES];
-  const long long i = (long long)blockIdx.x * IA_MO_THREADS + threadIdx.x;
-  int v = i < n ? load(i) : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (ia_lane() == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = 0;
-#pragma unroll
-    for (int w = 0; w < IA_MO_WAVES; w++) a += s_w[w];
-    bsum[blockIdx.x] = a;
-  }
-}
-
-// exclusive scan, in place, of the workgroup sums by one workgroup; the total goes to out0 and out1 (either may be null)
-__global__ __launch_bounds__(1024) void k_mo_scan_sums(int32_t *a, int n, int32_t *__restrict__ out0, int32_t *__restrict__ out1) {
-  __shared__ int s_w[16];
-  const int wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < n ? a[i] : 0;
-    int wave_total;
-    const int x = ia_wave_excl_scan(v, wave_total);
-    if (ia_lane() == 0) s_w[wave] = wave_total;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-      if (w < wave) before += s_w[w];
-      total += s_w[w];
-    }
-    if (i < n) a[i] = carry + before + x;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    if (out0) *out0 = carry;
-    if (out1) *out1 = carry;
-  }
-}
-
-template <class L>
-__global__ __launch_bounds__(IA_MO_THREADS) void k_mo_block_scan(L load, long long n, const int32_t *__restrict__ bsum,
-                                                                 int32_t *__restrict__ start) {
-  __shared__ int s_w[IA_MO_WAVES];
-  const long long i = (long long)blockIdx.x * IA_MO_THREADS + threadIdx.x;
-  const int v = i < n ? load(i) : 0;
-  int wave_total;
-  const int x = ia_wave_excl_scan(v, wave_total);
-  const int wave = threadIdx.x >> 6;
-  if (ia_lane() == 0) s_w[wave] = wave_total;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < IA_MO_WAVES; w++)
-    if (w < wave) base += s_w[w];
-  if (i < n) start[i] = bsum[blockIdx.x] + base + x;
-}
-
-// start[i] = sum of load(j) over j < i, i = 0 .. n (n >= 1); bsum: mo_blocks(n) ints of scratch; total: also written there (or null)
-template <class L>
-void mo_scan(L load, long long n, int32_t *bsum, int32_t *start, int32_t *total, hipStream_t s) {
-  const int nb = mo_blocks(n);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mo_block_sums<L>), dim3(nb), dim3(IA_MO_THREADS), 0, s, load, n, bsum);
-  hipLaunchKernelGGL(k_mo_scan_sums, dim3(1), dim3(1024), 0, s, bsum, nb, start + n, total);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mo_block_scan<L>), dim3(nb), dim3(IA_MO_THREADS), 0, s, load, n, (const int32_t *)bsum, start);
-}
-
-__global__ __launch_bounds__(IA_MO_THREADS) void k_mo_fill_i32(int32_t *__restrict__ p, long long n, int32_t value) {
-  const long long i = (long long)blockIdx.x * IA_MO_THREADS + threadIdx.x;
-  if (i < n) p[i] = value;
-}
-void mo_fill(int32_t *p, long long n, int32_t value, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_mo_fill_i32, dim3(mo_blocks(n)), dim3(IA_MO_THREADS), 0, s, p, n, value);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // segments: for every key its values, ascending
@@ -243,13 +150,13 @@ __global__ __launch_bounds__(64) void k_seg_sort_long(Seg S, int nk, int unique)
 // n_items >= 1, nk >= 1
 template <class E>
 void seg_build(const E &e, int n_items, int nk, Seg S, int32_t *bsum, bool unique, hipStream_t s) {
-  const dim3 b(IA_MO_THREADS), gi(mo_blocks(n_items));
-  mo_fill(S.cnt, nk, 0, s);
+  const dim3 b(IA_MO_THREADS), gi(ia_div_up(n_items, IA_MO_THREADS));
+  ia_fill_i32(S.cnt, nk, 0, s);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_emit<E, SinkCount>), gi, b, 0, s, e, n_items, SinkCount{S.cnt});
-  mo_scan(LoadInt{S.cnt}, nk, bsum, S.start, nullptr, s);
-  mo_fill(S.cnt, nk, 0, s);
+  ia_scan(LoadInt{S.cnt}, nk, bsum, S.start, nullptr, s);
+  ia_fill_i32(S.cnt, nk, 0, s);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_emit<E, SinkFill>), gi, b, 0, s, e, n_items, SinkFill{S});
-  hipLaunchKernelGGL(k_seg_sort, dim3(mo_blocks(nk)), b, 0, s, S, nk, unique ? 1 : 0);
+  hipLaunchKernelGGL(k_seg_sort, dim3(ia_div_up(nk, IA_MO_THREADS)), b, 0, s, S, nk, unique ? 1 : 0);
   hipLaunchKernelGGL(k_seg_sort_long, dim3(nk), dim3(64), 0, s, S, nk, unique ? 1 : 0);
 }
 
@@ -257,29 +164,21 @@ void seg_build(const E &e, int n_items, int nk, Seg S, int32_t *bsum, bool uniqu
 // faces and vertices
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool mo_finite3(const float *__restrict__ verts, int v) {
-  const float x = verts[(size_t)v * 3], y = verts[(size_t)v * 3 + 1], z = verts[(size_t)v * 3 + 2];
-  return __builtin_fabsf(x) < INFINITY && __builtin_fabsf(y) < INFINITY && __builtin_fabsf(z) < INFINITY;
+  return ia_finite3(verts[(size_t)v * 3], verts[(size_t)v * 3 + 1], verts[(size_t)v * 3 + 2]);
 }
 
 // the valid faces: indices in [0, nv), pairwise different, all three vertices finite (vok)
 __device__ __forceinline__ bool mo_face(const int32_t *__restrict__ faces, int f, int nv, const uint8_t *__restrict__ vok, int v[3]) {
-#pragma unroll
-  for (int e = 0; e < 3; e++) v[e] = faces[(size_t)f * 3 + e];
-  if ((uint32_t)v[0] >= (uint32_t)nv || (uint32_t)v[1] >= (uint32_t)nv || (uint32_t)v[2] >= (uint32_t)nv) return false;
-  if (v[0] == v[1] || v[1] == v[2] || v[0] == v[2]) return false;
+  ia_face_load(faces, f, v);
+  if (!ia_face_in_range(v, nv) || !ia_face_distinct(v)) return false;
   return vok[v[0]] && vok[v[1]] && vok[v[2]];
 }
 
 // n = (p1 - p0) x (p2 - p0) in fp64; p0 is returned as well
 __device__ __forceinline__ void mo_face_normal(const float *__restrict__ verts, const int v[3], double n[3], double p0[3]) {
   double p[3][3];
-#pragma unroll
-  for (int e = 0; e < 3; e++)
-#pragma unroll
-    for (int d = 0; d < 3; d++) p[e][d] = (double)verts[(size_t)v[e] * 3 + d];
-  const double u0 = p[1][0] - p[0][0], u1 = p[1][1] - p[0][1], u2 = p[1][2] - p[0][2];
-  const double w0 = p[2][0] - p[0][0], w1 = p[2][1] - p[0][1], w2 = p[2][2] - p[0][2];
-  n[0] = u1 * w2 - u2 * w1; n[1] = u2 * w0 - u0 * w2; n[2] = u0 * w1 - u1 * w0;
+  ia_face_corners(verts, v, p);
+  ia_face_cross(p, n);
   p0[0] = p[0][0]; p0[1] = p[0][1]; p0[2] = p[0][2];
 }
 
@@ -322,7 +221,7 @@ AdjWs adj_carve(void *ws, int nv, int nf) {
   o.nb.start = w.take<int32_t>(v + 1);
   o.nb.cnt = w.take<int32_t>(v);
   o.nb.vals = w.take<int32_t>(6 * f);
-  o.bsum = w.take<int32_t>((size_t)mo_blocks((long long)v + 1) + 1);
+  o.bsum = w.take<int32_t>((size_t)ia_div_up((long long)v + 1, IA_MO_THREADS) + 1);
   o.tmp = w.take<float>(3 * v);
   o.bytes = w.off;
   return o;
@@ -373,10 +272,10 @@ __global__ __launch_bounds__(IA_MO_THREADS) void k_vertex_normals(const float *_
     const int fv[3] = {faces[(size_t)f * 3], faces[(size_t)f * 3 + 1], faces[(size_t)f * 3 + 2]};   // valid: it was listed
     double c[3], p0[3];
     mo_face_normal(verts, fv, c, p0);
-    if (!(fabs(c[0]) < (double)INFINITY && fabs(c[1]) < (double)INFINITY && fabs(c[2]) < (double)INFINITY)) continue;
+    if (!ia_finite3(c[0], c[1], c[2])) continue;
     s[0] += c[0]; s[1] += c[1]; s[2] += c[2];
   }
-  const double len = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+  const double len = ia_len3d(s);
   const bool ok = len > 0.0 && len < (double)INFINITY;
 #pragma unroll
   for (int d = 0; d < 3; d++) normals[(size_t)v * 3 + d] = ok ? (float)(s[d] / len) : 0.f;
@@ -385,18 +284,8 @@ __global__ __launch_bounds__(IA_MO_THREADS) void k_vertex_normals(const float *_
 // ---------------------------------------------------------------------------------------------------------------------
 // clustering
 // ---------------------------------------------------------------------------------------------------------------------
-struct MoGrid { float lo[3]; float h, inv_h; int n[3]; };
-
-// cell of a point along one axis: clamp((int)floorf((p - lo) * inv_h), 0, n - 1), the clamp taken on the float so that no
-// conversion leaves the range of int
-__device__ __forceinline__ int mo_cell(float p, float lo, float inv_h, int n) {
-  const float t = floorf((p - lo) * inv_h);
-  if (!(t > 0.f)) return 0;
-  if (t >= (float)(n - 1)) return n - 1;
-  return (int)t;
-}
-
-__global__ __launch_bounds__(IA_MO_THREADS) void k_cl_cells(const float *__restrict__ verts, int nv, MoGrid G, uint8_t *__restrict__ vok,
+// (the grid and the cell of a coordinate: IaGrid, ia_grid_cell)
+__global__ __launch_bounds__(IA_MO_THREADS) void k_cl_cells(const float *__restrict__ verts, int nv, IaGrid G, uint8_t *__restrict__ vok,
                                                             int32_t *__restrict__ vclus, uint32_t *mask) {
   const long long v = (long long)blockIdx.x * IA_MO_THREADS + threadIdx.x;
   if (v >= nv) return;
@@ -404,9 +293,9 @@ __global__ __launch_bounds__(IA_MO_THREADS) void k_cl_cells(const float *__restr
   vok[v] = ok ? 1 : 0;
   int32_t key = -1;
   if (ok) {
-    const int i = mo_cell(verts[(size_t)v * 3], G.lo[0], G.inv_h, G.n[0]);
-    const int j = mo_cell(verts[(size_t)v * 3 + 1], G.lo[1], G.inv_h, G.n[1]);
-    const int k = mo_cell(verts[(size_t)v * 3 + 2], G.lo[2], G.inv_h, G.n[2]);
+    const int i = ia_grid_cell(verts[(size_t)v * 3], G.lo[0], G.inv_h, G.n[0]);
+    const int j = ia_grid_cell(verts[(size_t)v * 3 + 1], G.lo[1], G.inv_h, G.n[1]);
+    const int k = ia_grid_cell(verts[(size_t)v * 3 + 2], G.lo[2], G.inv_h, G.n[2]);
     key = (int32_t)(((long long)i * G.n[1] + j) * G.n[2] + k);         // < 2^27
     atomicOr(&mask[key >> 5], 1u << (key & 31));
   }
@@ -475,7 +364,7 @@ ClWs cl_carve(void *ws, int nv, int nf, long long cells) {
   o.fkeep = w.take<int32_t>(f);
   o.fbase = w.take<int32_t>(f + 1);
   const long long most = (long long)(v > f ? v : f) + 1 > o.words ? (long long)(v > f ? v : f) + 1 : o.words;
-  o.bsum = w.take<int32_t>((size_t)mo_blocks(most) + 1);
+  o.bsum = w.take<int32_t>((size_t)ia_div_up(most, IA_MO_THREADS) + 1);
   o.corner.start = w.take<int32_t>(v + 1);
   o.corner.cnt = w.take<int32_t>(v);
   o.corner.vals = w.take<int32_t>(3 * f);
@@ -507,7 +396,7 @@ __global__ __launch_bounds__(IA_MO_THREADS) void k_cl_emit_map(int nv, const int
 
 // one lane = one cluster: the quadric over its corners, the mean over its members, the regularised solve
 __global__ __launch_bounds__(IA_MO_THREADS) void k_cl_solve(const float *__restrict__ verts, const int32_t *__restrict__ faces,
-                                                            const float *__restrict__ colors, int nv, MoGrid G, double reg,
+                                                            const float *__restrict__ colors, int nv, IaGrid G, double reg,
                                                             const int32_t *__restrict__ used, const int32_t *__restrict__ cbase, Seg corner,
                                                             Seg member, float *__restrict__ verts_out, float *__restrict__ colors_out, int cap) {
   const long long c = (long long)blockIdx.x * IA_MO_THREADS + threadIdx.x;
@@ -522,7 +411,7 @@ __global__ __launch_bounds__(IA_MO_THREADS) void k_cl_solve(const float *__restr
     const int v0 = mem[0];
 #pragma unroll
     for (int d = 0; d < 3; d++)
-      o[d] = (double)G.lo[d] + ((double)mo_cell(verts[(size_t)v0 * 3 + d], G.lo[d], G.inv_h, G.n[d]) + 0.5) * h;
+      o[d] = (double)G.lo[d] + ((double)ia_grid_cell(verts[(size_t)v0 * 3 + d], G.lo[d], G.inv_h, G.n[d]) + 0.5) * h;
   }
   double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
   const int nc = corner.cnt[c];
@@ -532,7 +421,7 @@ __global__ __launch_bounds__(IA_MO_THREADS) void k_cl_solve(const float *__restr
     const int fv[3] = {faces[(size_t)f * 3], faces[(size_t)f * 3 + 1], faces[(size_t)f * 3 + 2]};
     double n[3], p0[3];
     mo_face_normal(verts, fv, n, p0);
-    const double L = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double L = ia_len3d(n);
     if (!(L > 0.0 && L < (double)INFINITY)) continue;
     const double g0 = n[0] / L, g1 = n[1] / L, g2 = n[2] / L, a = L * 0.5;
     const double d = -(g0 * (p0[0] - o[0]) + g1 * (p0[1] - o[1]) + g2 * (p0[2] - o[2]));
@@ -580,29 +469,13 @@ __global__ __launch_bounds__(IA_MO_THREADS) void k_cl_solve(const float *__restr
   }
 }
 
-// the box, the cell edge and the sizes, checked; the grid and its number of cells
-int cl_check(const char *who, int nv, int nf, const float lo[3], const float hi[3], float h, float inv_h, MoGrid *G, long long *cells) {
+// the sizes, the box and the cell edge, checked; the grid and its number of cells
+static_assert(IA_CLUSTER_MAX_CELLS == 1ll << 27, "the text below");
+int cl_check(const char *who, int nv, int nf, const float lo[3], const float hi[3], float h, float inv_h, IaGrid *G, long long *cells) {
   IA_CHECK_ARG(nv >= 0 && nf >= 0, "%s: negative size", who);
   IA_CHECK_ARG(nf <= IA_MESHOPS_MAX_FACES, "%s: nf = %d above %d, the most whose 6 nf neighbour entries an int32 offset reaches", who, nf,
                IA_MESHOPS_MAX_FACES);
-  IA_CHECK_ARG(h > 0.f && h < INFINITY, "%s: the cell edge h = %g must be positive and finite", who, (double)h);
-  IA_CHECK_ARG(inv_h > 0.f && inv_h < INFINITY, "%s: inv_h = %g must be positive and finite", who, (double)inv_h);
-  double total = 1.0;
-  for (int d = 0; d < 3; d++) {
-    IA_CHECK_ARG(fabsf(lo[d]) < INFINITY && fabsf(hi[d]) < INFINITY, "%s: the box is not finite", who);
-    double n = ceil(((double)hi[d] - (double)lo[d]) / (double)h);
-    if (!(n >= 1.0)) n = 1.0;
-    IA_CHECK_ARG(n <= (double)IA_CLUSTER_MAX_CELLS, "%s: a grid of more than 2^27 cells (axis %d alone has %.0f): enlarge h", who, d, n);
-    G->lo[d] = lo[d];
-    G->n[d] = (int)n;
-    total *= n;
-  }
-  IA_CHECK_ARG(total <= (double)IA_CLUSTER_MAX_CELLS, "%s: a grid of %d x %d x %d cells is more than 2^27: enlarge h", who, G->n[0], G->n[1],
-               G->n[2]);
-  G->h = h;
-  G->inv_h = inv_h;
-  *cells = (long long)G->n[0] * G->n[1] * G->n[2];
-  return IA_OK;
+  return ia_grid_check(who, lo, hi, h, inv_h, false, IA_CLUSTER_MAX_CELLS, "2^27", G, cells);
 }
 
 __global__ void k_mo_set2(int32_t *p, int32_t a, int32_t b) { p[0] = a; p[1] = b; }
@@ -627,14 +500,14 @@ extern "C" int ia_mesh_adjacency_build(const float *verts, const int32_t *faces,
   if (nv == 0) return IA_OK;
   hipStream_t s = (hipStream_t)stream;
   if (nf == 0) {                 // no face: every list is empty
-    mo_fill(W.inc.cnt, nv, 0, s);
-    mo_fill(W.inc.start, (long long)nv + 1, 0, s);
-    mo_fill(W.nb.cnt, nv, 0, s);
-    mo_fill(W.nb.start, (long long)nv + 1, 0, s);
-    IA_LAUNCH_CHECK("k_mo_fill_i32");
+    ia_fill_i32(W.inc.cnt, nv, 0, s);
+    ia_fill_i32(W.inc.start, (long long)nv + 1, 0, s);
+    ia_fill_i32(W.nb.cnt, nv, 0, s);
+    ia_fill_i32(W.nb.start, (long long)nv + 1, 0, s);
+    IA_LAUNCH_CHECK("k_fill_i32");
     return IA_OK;
   }
-  hipLaunchKernelGGL(k_mo_vok, dim3(mo_blocks(nv)), dim3(IA_MO_THREADS), 0, s, verts, nv, W.vok);
+  hipLaunchKernelGGL(k_mo_vok, dim3(ia_div_up(nv, IA_MO_THREADS)), dim3(IA_MO_THREADS), 0, s, verts, nv, W.vok);
   seg_build(EmitFaceIncidence{faces, W.vok, nv}, nf, nv, W.inc, W.bsum, false, s);
   seg_build(EmitFaceNeighbours{faces, W.vok, nv}, nf, nv, W.nb, W.bsum, true, s);
   IA_LAUNCH_CHECK("k_seg_sort");
@@ -652,9 +525,9 @@ extern "C" int ia_mesh_taubin(const float *verts, int nv, int nf, void *ws, size
   const AdjWs W = adj_carve(ws, nv, nf);
   if (ws_bytes < W.bytes) return ia_set_error(IA_ERR_WORKSPACE, "ia_mesh_taubin: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const dim3 b(IA_MO_THREADS), g(mo_blocks(nv));
+  const dim3 b(IA_MO_THREADS), g(ia_div_up(nv, IA_MO_THREADS));
   if (iters == 0)
-    hipLaunchKernelGGL(k_mo_copy_u32, dim3(mo_blocks(3ll * nv)), b, 0, s, reinterpret_cast<const uint32_t *>(verts), 3ll * nv,
+    hipLaunchKernelGGL(k_mo_copy_u32, dim3(ia_div_up(3ll * nv, IA_MO_THREADS)), b, 0, s, reinterpret_cast<const uint32_t *>(verts), 3ll * nv,
                        reinterpret_cast<uint32_t *>(out));
   const float *src = verts;
   for (int it = 0; it < iters; it++) {
@@ -674,7 +547,7 @@ extern "C" int ia_mesh_vertex_normals(const float *verts, const int32_t *faces, 
   IA_CHECK_ARG(verts && normals && ws && (nf == 0 || faces), "ia_mesh_vertex_normals: null pointer");
   const AdjWs W = adj_carve(const_cast<void *>(ws), nv, nf);
   if (ws_bytes < W.bytes) return ia_set_error(IA_ERR_WORKSPACE, "ia_mesh_vertex_normals: workspace too small");
-  hipLaunchKernelGGL(k_vertex_normals, dim3(mo_blocks(nv)), dim3(IA_MO_THREADS), 0, (hipStream_t)stream, verts, faces, nv,
+  hipLaunchKernelGGL(k_vertex_normals, dim3(ia_div_up(nv, IA_MO_THREADS)), dim3(IA_MO_THREADS), 0, (hipStream_t)stream, verts, faces, nv,
                      (const int32_t *)W.inc.start, (const int32_t *)W.inc.cnt, (const int32_t *)W.inc.vals, normals);
   IA_LAUNCH_CHECK("k_vertex_normals");
   return IA_OK;
@@ -689,7 +562,7 @@ extern "C" int ia_mesh_cluster_count(const float *verts, const int32_t *faces, i
                                      float hi_x, float hi_y, float hi_z, float h, float inv_h, void *ws, size_t ws_bytes, int32_t *counts,
                                      void *stream) {
   const float lo[3] = {lo_x, lo_y, lo_z}, hi[3] = {hi_x, hi_y, hi_z};
-  MoGrid G;
+  IaGrid G;
   long long cells;
   const int rc = cl_check("ia_mesh_cluster_count", nv, nf, lo, hi, h, inv_h, &G, &cells);
   if (rc) return rc;
@@ -702,15 +575,15 @@ extern "C" int ia_mesh_cluster_count(const float *verts, const int32_t *faces, i
     IA_LAUNCH_CHECK("k_mo_set2");
     return IA_OK;
   }
-  const dim3 b(IA_MO_THREADS), gv(mo_blocks(nv)), gf(mo_blocks(nf));
-  mo_fill(reinterpret_cast<int32_t *>(W.mask), W.words, 0, s);
-  mo_fill(W.used, nv, 0, s);
+  const dim3 b(IA_MO_THREADS), gv(ia_div_up(nv, IA_MO_THREADS)), gf(ia_div_up(nf, IA_MO_THREADS));
+  ia_fill_i32(reinterpret_cast<int32_t *>(W.mask), W.words, 0, s);
+  ia_fill_i32(W.used, nv, 0, s);
   hipLaunchKernelGGL(k_cl_cells, gv, b, 0, s, verts, nv, G, W.vok, W.vclus, W.mask);
-  mo_scan(LoadPopc{W.mask}, W.words, W.bsum, W.wbase, nullptr, s);
+  ia_scan(LoadPopc{W.mask}, W.words, W.bsum, W.wbase, nullptr, s);
   hipLaunchKernelGGL(k_cl_rank, gv, b, 0, s, nv, (const uint32_t *)W.mask, (const int32_t *)W.wbase, W.vclus);
   hipLaunchKernelGGL(k_cl_mark_faces, gf, b, 0, s, faces, nf, nv, (const uint8_t *)W.vok, (const int32_t *)W.vclus, W.fkeep, W.used);
-  mo_scan(LoadInt{W.fkeep}, nf, W.bsum, W.fbase, counts + 1, s);
-  mo_scan(LoadInt{W.used}, nv, W.bsum, W.cbase, counts, s);
+  ia_scan(LoadInt{W.fkeep}, nf, W.bsum, W.fbase, counts + 1, s);
+  ia_scan(LoadInt{W.used}, nv, W.bsum, W.cbase, counts, s);
   seg_build(EmitClusterCorners{faces, W.vok, W.vclus, nv}, nf, nv, W.corner, W.bsum, false, s);
   seg_build(EmitClusterMembers{W.vclus}, nv, nv, W.member, W.bsum, false, s);
   IA_LAUNCH_CHECK("k_seg_sort");
@@ -722,7 +595,7 @@ extern "C" int ia_mesh_cluster_emit(const float *verts, const int32_t *faces, co
                                     size_t ws_bytes, float *verts_out, int nv_out, int32_t *faces_out, int nf_out, float *colors_out,
                                     int32_t *vert_cluster, void *stream) {
   const float lo[3] = {lo_x, lo_y, lo_z}, hi[3] = {hi_x, hi_y, hi_z};
-  MoGrid G;
+  IaGrid G;
   long long cells;
   const int rc = cl_check("ia_mesh_cluster_emit", nv, nf, lo, hi, h, inv_h, &G, &cells);
   if (rc) return rc;
@@ -736,11 +609,11 @@ extern "C" int ia_mesh_cluster_emit(const float *verts, const int32_t *faces, co
   hipStream_t s = (hipStream_t)stream;
   if (nv == 0) return IA_OK;
   if (nf == 0) {
-    if (vert_cluster) mo_fill(vert_cluster, nv, -1, s);
-    IA_LAUNCH_CHECK("k_mo_fill_i32");
+    if (vert_cluster) ia_fill_i32(vert_cluster, nv, -1, s);
+    IA_LAUNCH_CHECK("k_fill_i32");
     return IA_OK;
   }
-  const dim3 b(IA_MO_THREADS), gv(mo_blocks(nv)), gf(mo_blocks(nf));
+  const dim3 b(IA_MO_THREADS), gv(ia_div_up(nv, IA_MO_THREADS)), gf(ia_div_up(nf, IA_MO_THREADS));
   if (vert_cluster)
     hipLaunchKernelGGL(k_cl_emit_map, gv, b, 0, s, nv, (const int32_t *)W.vclus, (const int32_t *)W.used, (const int32_t *)W.cbase, vert_cluster);
   if (nf_out > 0)

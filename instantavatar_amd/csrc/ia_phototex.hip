@@ -1,5 +1,5 @@
 // ia_phototex.hip -- a photo texture (no counterpart in the reference): the frames a sequence was recorded with, projected back onto
-// the texture atlas of the mesh (layout of ia_texture.hip, camera of ia_raster.hip).
+// the texture atlas of the mesh (layout of ia_mesh_dev.h, the one ia_texture.hip bakes through; camera of ia_raster.hip).
 //   zero-fill of the fp64 accumulator                                       (ia_phototex_zero)
 //   a chunk of frames added to a range of texels                            (ia_phototex_accumulate)
 //   the weighted mean, the fallback atlas and the per-texel frame count     (ia_phototex_resolve)
@@ -12,6 +12,7 @@
 // posed corners take two values per wave and the camera rows are uniform.  A lane keeps S, W and seen of its texel in registers over
 // the frames of the call and touches its record once.
 #include "ia_common.h"
+#include "ia_mesh_dev.h"
 #include "../../include/instantavatar_hip_phototex.h"
 #include "../../include/instantavatar_hip_texture.h"
 
@@ -29,27 +30,21 @@ struct PhotoCamera {
   double fx, fy, cx, cy, near;
 };
 
-__device__ __forceinline__ bool ptx_finite3(double x, double y, double z) {
-  return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
-
 __global__ __launch_bounds__(IA_PHOTOTEX_THREADS) void k_phototex_zero(unsigned long long *__restrict__ acc, long long words) {
   const long long i = (long long)blockIdx.x * IA_PHOTOTEX_THREADS + threadIdx.x;
   if (i < words) acc[i] = 0ull;
 }
 
-// the contribution of frame `fr` to one texel with weights (u0, u1, u2) on the face (ia, ib, ic); false: nothing
-__device__ __forceinline__ bool ptx_frame(const float *__restrict__ verts, int nv, int ia, int ib, int ic, double u0, double u1, double u2,
-                                          int fr, const float *__restrict__ w2c, const PhotoCamera &cam,
+// the contribution of frame `fr` to one texel with weights bw on the face with corners idx; false: nothing
+__device__ __forceinline__ bool ptx_frame(const float *__restrict__ verts, int nv, const int idx[3], const double bw[3], int fr, const float *__restrict__ w2c, const PhotoCamera &cam,
                                           const uint8_t *__restrict__ images, const float *__restrict__ masks,
                                           const float *__restrict__ depth, int H, int W, double cos_min, double power, double depth_tol,
                                           double &r0, double &r1, double &r2, double &wgt) {
-  const float *v = verts + (size_t)fr * nv * 3;
-  const double a0 = v[3 * (size_t)ia], a1 = v[3 * (size_t)ia + 1], a2 = v[3 * (size_t)ia + 2];
-  const double b0 = v[3 * (size_t)ib], b1 = v[3 * (size_t)ib + 1], b2 = v[3 * (size_t)ib + 2];
-  const double c0 = v[3 * (size_t)ic], c1 = v[3 * (size_t)ic + 1], c2 = v[3 * (size_t)ic + 2];
-  if (!(ptx_finite3(a0, a1, a2) && ptx_finite3(b0, b1, b2) && ptx_finite3(c0, c1, c2))) return false;
-  const double p0 = u0 * a0 + u1 * b0 + u2 * c0, p1 = u0 * a1 + u1 * b1 + u2 * c1, p2 = u0 * a2 + u1 * b2 + u2 * c2;
+  double c3[3][3], pt[3], m[3];
+  ia_face_corners(verts + (size_t)fr * nv * 3, idx, c3);
+  if (!ia_corners_finite(c3)) return false;
+  ia_face_point(c3, bw, pt);
+  const double p0 = pt[0], p1 = pt[1], p2 = pt[2];
   const float *M = w2c + 16 * (size_t)fr;
   const double R00 = M[0], R01 = M[1], R02 = M[2], R10 = M[4], R11 = M[5], R12 = M[6], R20 = M[8], R21 = M[9], R22 = M[10];
   const double x0 = R00 * p0 + R01 * p1 + R02 * p2 + (double)M[3];
@@ -59,11 +54,10 @@ __device__ __forceinline__ bool ptx_frame(const float *__restrict__ verts, int n
   const double u = cam.fx * x0 / x2 + cam.cx, vv = cam.fy * x1 / x2 + cam.cy;
   if (!(u >= 0.0 && u < (double)(W - 1) && vv >= 0.0 && vv < (double)(H - 1))) return false;      // NaN fails
   // facing
-  const double e0 = b0 - a0, e1 = b1 - a1, e2 = b2 - a2, g0 = c0 - a0, g1 = c1 - a1, g2 = c2 - a2;
-  const double m0 = e1 * g2 - e2 * g1, m1 = e2 * g0 - e0 * g2, m2 = e0 * g1 - e1 * g0;
-  const double len = sqrt(m0 * m0 + m1 * m1 + m2 * m2);
+  ia_face_cross(c3, m);
+  const double len = ia_len3d(m);
   if (!(len > 0.0 && __builtin_isfinite(len))) return false;
-  const double n0 = m0 / len, n1 = m1 / len, n2 = m2 / len;
+  const double n0 = m[0] / len, n1 = m[1] / len, n2 = m[2] / len;
   const double q0 = R00 * n0 + R01 * n1 + R02 * n2, q1 = R10 * n0 + R11 * n1 + R12 * n2, q2 = R20 * n0 + R21 * n1 + R22 * n2;
   const double c = -(q0 * x0 + q1 * x1 + q2 * x2) / sqrt(x0 * x0 + x1 * x1 + x2 * x2);
   if (!(c > cos_min)) return false;
@@ -100,28 +94,24 @@ __global__ __launch_bounds__(IA_PHOTOTEX_THREADS) void k_phototex_accumulate(
     const float *__restrict__ depth, int H, int W, double cos_min, double power, double depth_tol, PhotoRecord *__restrict__ acc, int br0) {
   const int bc = blockIdx.x, br = br0 + blockIdx.y;
   const int nb = T / B;
-  const double L = (double)(B - 3);
   for (int k = threadIdx.x; k < B * B; k += blockDim.x) {
     int j = k / B, i = k - j * B;
     const long long g = (long long)(br * B + j) * T + (bc * B + i);           // < T^2 <= 2^28
     if (g < first || g >= (long long)first + count) continue;
-    const int h = i + j <= B - 2 ? 0 : 1;
-    const int f = 2 * (br * nb + bc) + h;                                      // < 2 (T / B)^2 <= 2^25
+    const int h = ia_atlas_half(B, i, j);
+    const int f = ia_atlas_face(br, bc, nb, h);
     if (f >= nf) continue;
-    const int ia = faces[3 * (size_t)f], ib = faces[3 * (size_t)f + 1], ic = faces[3 * (size_t)f + 2];
-    if (ia < 0 || ia >= nv || ib < 0 || ib >= nv || ic < 0 || ic >= nv) continue;
-    if (h) {
-      i = B - 1 - i;
-      j = B - 1 - j;
-    }
-    const double u1 = (double)i / L, u2 = (double)j / L, u0 = 1.0 - u1 - u2;
+    int idx[3];
+    ia_face_load(faces, f, idx);
+    if (!ia_face_in_range(idx, nv)) continue;
+    double u[3];
+    ia_atlas_weights(B, i, j, u);
     PhotoRecord *rec = acc + (size_t)(g - first);
     double s0 = rec->s0, s1 = rec->s1, s2 = rec->s2, w = rec->w;
     int seen = rec->seen;
     for (int fr = 0; fr < F; fr++) {
       double r0, r1, r2, wgt;
-      if (ptx_frame(verts, nv, ia, ib, ic, u0, u1, u2, fr, w2c, cam, images, masks, depth, H, W, cos_min, power, depth_tol, r0, r1, r2,
-                    wgt)) {
+      if (ptx_frame(verts, nv, idx, u, fr, w2c, cam, images, masks, depth, H, W, cos_min, power, depth_tol, r0, r1, r2, wgt)) {
         s0 += wgt * r0;
         s1 += wgt * r1;
         s2 += wgt * r2;
@@ -168,8 +158,6 @@ __global__ __launch_bounds__(IA_PHOTOTEX_THREADS) void k_phototex_resolve(const 
   if (ia_lane() == 0 && b) atomicAdd(unseen, __popcll(b));
 }
 
-inline int ptx_blocks(long long n) { return (int)((n + IA_PHOTOTEX_THREADS - 1) / IA_PHOTOTEX_THREADS); }
-
 }  // namespace
 
 extern "C" size_t ia_phototex_acc_bytes(int count) { return count < 0 ? 0 : (size_t)count * IA_PHOTOTEX_ACC_STRIDE; }
@@ -180,7 +168,7 @@ extern "C" int ia_phototex_zero(void *acc, int count, void *stream) {
   IA_CHECK_ARG(acc, "ia_phototex_zero: null pointer");
   IA_CHECK_ARG(((uintptr_t)acc & 7) == 0, "ia_phototex_zero: the accumulator is not 8-byte aligned");
   const long long words = (long long)count * (IA_PHOTOTEX_ACC_STRIDE / 8);
-  hipLaunchKernelGGL(k_phototex_zero, dim3(ptx_blocks(words)), dim3(IA_PHOTOTEX_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_phototex_zero, dim3(ia_div_up(words, IA_PHOTOTEX_THREADS)), dim3(IA_PHOTOTEX_THREADS), 0, (hipStream_t)stream,
                      (unsigned long long *)acc, words);
   IA_LAUNCH_CHECK("k_phototex_zero");
   return IA_OK;
@@ -230,7 +218,7 @@ extern "C" int ia_phototex_resolve(const void *acc, const float *base, const int
   if (count == 0) return IA_OK;
   IA_CHECK_ARG(acc && owner && atlas && seen && unseen, "ia_phototex_resolve: null pointer");
   IA_CHECK_ARG(((uintptr_t)acc & 7) == 0, "ia_phototex_resolve: the accumulator is not 8-byte aligned");
-  hipLaunchKernelGGL(k_phototex_resolve, dim3(ptx_blocks(count)), dim3(IA_PHOTOTEX_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_phototex_resolve, dim3(ia_div_up(count, IA_PHOTOTEX_THREADS)), dim3(IA_PHOTOTEX_THREADS), 0, (hipStream_t)stream,
                      (const PhotoRecord *)acc, base, owner, count, min_frames, atlas, seen, unseen);
   IA_LAUNCH_CHECK("k_phototex_resolve");
   return IA_OK;

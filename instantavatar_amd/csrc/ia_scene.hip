@@ -14,6 +14,7 @@
 // key +inf, colour, opacity and depth term 0, which leave C, D and T bit-for-bit unchanged) are ordered by an insertion sort
 // unrolled into compare-exchanges on registers -- no runtime-indexed array, no branch.
 #include "ia_common.h"
+#include "ia_mesh_dev.h"
 #include "../../include/instantavatar_hip_scene.h"
 
 #define IA_SCENE_THREADS 256
@@ -24,8 +25,6 @@ struct ScenePlane {          // the plane, the disc, the checker and the in-plan
   double n[3], h, centre[3], r0, r1, cell, e1[3], e2[3];
   float g0[3], g1[3];
 };
-
-__device__ __forceinline__ double scn_dot(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 __device__ __forceinline__ bool scn_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }      // false for NaN
 
@@ -41,18 +40,18 @@ __global__ __launch_bounds__(IA_SCENE_THREADS) void k_scene_ground(const float *
   if (r >= R) return;
   const size_t r3 = 3 * (size_t)r;
   const double o[3] = {rays_o[r3], rays_o[r3 + 1], rays_o[r3 + 2]}, d[3] = {rays_d[r3], rays_d[r3 + 1], rays_d[r3 + 2]};
-  const double no = scn_dot(pl.n, o), nd = scn_dot(pl.n, d);
+  const double no = ia_dot3d(pl.n, o), nd = ia_dot3d(pl.n, d);
   const double t = (pl.h - no) / nd;
   const float tf = (float)t;
   float t_out = 0.f, a_out = 0.f, c_out[3] = {0.f, 0.f, 0.f}, p_out[3] = {0.f, 0.f, 0.f};
   if (no > pl.h && nd < 0.0 && scn_finite(tf) && tf > 0.f) {
     const double p[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
     const double q[3] = {p[0] - pl.centre[0], p[1] - pl.centre[1], p[2] - pl.centre[2]};
-    const double rho = sqrt(scn_dot(q, q));
+    const double rho = sqrt(ia_dot3d(q, q));
     const double a = rho <= pl.r0 ? 1.0 : (rho >= pl.r1 ? 0.0 : (pl.r1 - rho) / (pl.r1 - pl.r0));
     bool odd = false;
     if (pl.cell > 0.0) {
-      double fu = floor(scn_dot(q, pl.e1) / pl.cell), fv = floor(scn_dot(q, pl.e2) / pl.cell);
+      double fu = floor(ia_dot3d(q, pl.e1) / pl.cell), fv = floor(ia_dot3d(q, pl.e2) / pl.cell);
       if (!(fabs(fu) < 4611686018427387904.0)) fu = 0.0;      // 2^62: beyond it a floor counts as 0 (also NaN)
       if (!(fabs(fv) < 4611686018427387904.0)) fv = 0.0;
       odd = (((long long)fu + (long long)fv) & 1ll) != 0;
@@ -228,8 +227,6 @@ __global__ __launch_bounds__(IA_SCENE_THREADS) void k_scene_composite(
   if (ia_lane() == 0 && b) atomicAdd(contested, __popcll(b));
 }
 
-inline int scn_blocks(long long n) { return (int)((n + IA_SCENE_THREADS - 1) / IA_SCENE_THREADS); }
-
 inline bool scn_finite_h(double x) { return __builtin_isfinite(x); }
 
 }  // namespace
@@ -239,7 +236,7 @@ extern "C" int ia_scene_zero(int32_t *words, int n, void *stream) {
   if (n == 0) return IA_OK;
   IA_CHECK_ARG(words, "ia_scene_zero: null pointer");
   IA_CHECK_ARG(((uintptr_t)words & 3) == 0, "ia_scene_zero: the words are not 4-byte aligned");
-  hipLaunchKernelGGL(k_scene_zero, dim3(scn_blocks(n)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, words, n);
+  hipLaunchKernelGGL(k_scene_zero, dim3(ia_div_up(n, IA_SCENE_THREADS)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, words, n);
   IA_LAUNCH_CHECK("k_scene_zero");
   return IA_OK;
 }
@@ -278,7 +275,7 @@ extern "C" int ia_scene_ground(const float *rays_o, const float *rays_d, int R, 
   pl.e2[0] = n[1] * pl.e1[2] - n[2] * pl.e1[1];
   pl.e2[1] = n[2] * pl.e1[0] - n[0] * pl.e1[2];
   pl.e2[2] = n[0] * pl.e1[1] - n[1] * pl.e1[0];
-  hipLaunchKernelGGL(k_scene_ground, dim3(scn_blocks(R)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, rays_o, rays_d, R, pl, t_g, a_g,
+  hipLaunchKernelGGL(k_scene_ground, dim3(ia_div_up(R, IA_SCENE_THREADS)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, rays_o, rays_d, R, pl, t_g, a_g,
                      c_g, P);
   IA_LAUNCH_CHECK("k_scene_ground");
   return IA_OK;
@@ -295,7 +292,7 @@ extern "C" int ia_scene_shadow(const float *P, const float *a_g, int R, const fl
   IA_CHECK_ARG(near > 0.f && scn_finite_h(near), "%s: near must be positive and finite", who);
   if (R == 0) return IA_OK;
   IA_CHECK_ARG(P && a_g && maps && proj && shade, "%s: null pointer", who);
-  hipLaunchKernelGGL(k_scene_shadow, dim3(scn_blocks(R)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, P, a_g, R, maps, proj, K, S,
+  hipLaunchKernelGGL(k_scene_shadow, dim3(ia_div_up(R, IA_SCENE_THREADS)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, P, a_g, R, maps, proj, K, S,
                      radius, strength, (double)near, shade);
   IA_LAUNCH_CHECK("k_scene_shadow");
   return IA_OK;
@@ -312,7 +309,7 @@ extern "C" int ia_scene_composite(const float *c, const float *a, const float *d
   IA_CHECK_ARG(ng == 0 || ng == 4, "%s: the ground needs t_g, a_g, c_g and shade, or none of them", who);
   if (R == 0) return IA_OK;
   IA_CHECK_ARG(c && a && d && rgb && alpha && depth && contested, "%s: null pointer", who);
-  const dim3 grid(scn_blocks(R)), block(IA_SCENE_THREADS);
+  const dim3 grid(ia_div_up(R, IA_SCENE_THREADS)), block(IA_SCENE_THREADS);
   hipStream_t s = (hipStream_t)stream;
 #define SCN_LAUNCH(KK)                                                                                                              \
   case KK:                                                                                                                          \

@@ -7,14 +7,14 @@
 // The definitions are stated in DESIGN.md section 4 ("texture atlas") and in include/instantavatar_hip_texture.h.  Streaming
 // kernels: one thread per texel, corner or pixel, consecutive threads on consecutive addresses, no LDS.  Nothing here synchronises,
 // allocates or reads on the host; the only atomic adds integers, so two calls on the same input give the same bytes.
+// The layout of the atlas (which half and face own a texel, the texel's weights) and the face pieces are ia_mesh_dev.h's.
 #include "ia_common.h"
+#include "ia_mesh_dev.h"
 #include "../../include/instantavatar_hip_texture.h"
 
 #define IA_TEX_THREADS 256
 
 namespace {
-
-inline int tex_blocks(long long n) { return (int)((n + IA_TEX_THREADS - 1) / IA_TEX_THREADS); }
 
 // blocks per atlas row: max(1, ceil(sqrt(ceil(nf / 2)))) in integers
 inline int tex_blocks_per_row(int nf) {
@@ -46,10 +46,6 @@ __global__ __launch_bounds__(IA_TEX_THREADS) void k_tex_corner_uv(int nf, int B,
   uv[2 * (size_t)i + 1] = (float)((q / nb) * B + y) + 0.5f;
 }
 
-__device__ __forceinline__ bool tex_finite3(double x, double y, double z) {
-  return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
-
 __global__ __launch_bounds__(IA_TEX_THREADS) void k_tex_texel_points(const float *__restrict__ verts, int nv,
                                                                      const int32_t *__restrict__ faces, int nf, int B, int T, int first,
                                                                      int count, const float *__restrict__ t, float t_scalar,
@@ -61,53 +57,40 @@ __global__ __launch_bounds__(IA_TEX_THREADS) void k_tex_texel_points(const float
   const int y = g / T, x = g - y * T;
   const int bc = x / B, br = y / B;
   int i = x - bc * B, j = y - br * B;
-  const int h = i + j <= B - 2 ? 0 : 1;
-  int f = 2 * (br * (T / B) + bc) + h;                           // < 2 (T / B)^2 <= 2^25
-  double p0 = 0, p1 = 0, p2 = 0, n0 = 0, n1 = 0, n2 = 0;
+  const int h = ia_atlas_half(B, i, j);
+  int f = ia_atlas_face(br, bc, T / B, h);
+  double pt[3] = {0, 0, 0}, n[3] = {0, 0, 0};
   if (f >= nf) f = -1;
   if (f >= 0) {
-    const int ia = faces[3 * (size_t)f], ib = faces[3 * (size_t)f + 1], ic = faces[3 * (size_t)f + 2];
-    if (ia < 0 || ia >= nv || ib < 0 || ib >= nv || ic < 0 || ic >= nv) {
+    int v[3];
+    double p[3][3];
+    ia_face_load(faces, f, v);
+    bool ok = ia_face_in_range(v, nv);
+    if (ok) {
+      ia_face_corners(verts, v, p);
+      ok = ia_corners_finite(p);
+    }
+    if (!ok) {
       f = -1;
     } else {
-      const double a0 = verts[3 * (size_t)ia], a1 = verts[3 * (size_t)ia + 1], a2 = verts[3 * (size_t)ia + 2];
-      const double b0 = verts[3 * (size_t)ib], b1 = verts[3 * (size_t)ib + 1], b2 = verts[3 * (size_t)ib + 2];
-      const double c0 = verts[3 * (size_t)ic], c1 = verts[3 * (size_t)ic + 1], c2 = verts[3 * (size_t)ic + 2];
-      if (!(tex_finite3(a0, a1, a2) && tex_finite3(b0, b1, b2) && tex_finite3(c0, c1, c2))) {
-        f = -1;
-      } else {
-        if (h) {
-          i = B - 1 - i;
-          j = B - 1 - j;
-        }
-        const double L = (double)(B - 3);
-        const double u1 = (double)i / L, u2 = (double)j / L, u0 = 1.0 - u1 - u2;
-        p0 = u0 * a0 + u1 * b0 + u2 * c0;
-        p1 = u0 * a1 + u1 * b1 + u2 * c1;
-        p2 = u0 * a2 + u1 * b2 + u2 * c2;
-        const double e0 = b0 - a0, e1 = b1 - a1, e2 = b2 - a2, g0 = c0 - a0, g1 = c1 - a1, g2 = c2 - a2;
-        const double m0 = e1 * g2 - e2 * g1, m1 = e2 * g0 - e0 * g2, m2 = e0 * g1 - e1 * g0;
-        const double len = sqrt(m0 * m0 + m1 * m1 + m2 * m2);
-        if (len > 0.0 && __builtin_isfinite(len)) {
-          n0 = m0 / len;
-          n1 = m1 / len;
-          n2 = m2 / len;
-        }
-        const double tt = (double)t_scalar + (t ? (double)t[idx] : 0.0);
-        p0 += tt * n0;
-        p1 += tt * n1;
-        p2 += tt * n2;
+      double u[3], m[3];
+      ia_atlas_weights(B, i, j, u);
+      ia_face_point(p, u, pt);
+      ia_face_cross(p, m);
+      const double len = ia_len3d(m);
+      if (len > 0.0 && __builtin_isfinite(len)) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) n[d] = m[d] / len;
       }
+      const double tt = (double)t_scalar + (t ? (double)t[idx] : 0.0);
+#pragma unroll
+      for (int d = 0; d < 3; d++) pt[d] += tt * n[d];
     }
   }
-  if (f < 0) p0 = p1 = p2 = n0 = n1 = n2 = 0.0;
-  pts[3 * (size_t)idx] = (float)p0;
-  pts[3 * (size_t)idx + 1] = (float)p1;
-  pts[3 * (size_t)idx + 2] = (float)p2;
-  if (normal) {
-    normal[3 * (size_t)idx] = (float)n0;
-    normal[3 * (size_t)idx + 1] = (float)n1;
-    normal[3 * (size_t)idx + 2] = (float)n2;
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    pts[3 * (size_t)idx + d] = (float)pt[d];
+    if (normal) normal[3 * (size_t)idx + d] = (float)n[d];
   }
   if (owner) owner[idx] = f;
 }
@@ -194,7 +177,7 @@ extern "C" int ia_tex_corner_uv(int nf, int B, int T, float *uv, void *stream) {
   if (int rc = tex_check_layout("ia_tex_corner_uv", nf, B, T)) return rc;
   if (nf == 0) return IA_OK;
   IA_CHECK_ARG(uv, "ia_tex_corner_uv: null pointer");
-  hipLaunchKernelGGL(k_tex_corner_uv, dim3(tex_blocks(3ll * nf)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, nf, B, T / B, uv);
+  hipLaunchKernelGGL(k_tex_corner_uv, dim3(ia_div_up(3ll * nf, IA_TEX_THREADS)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, nf, B, T / B, uv);
   IA_LAUNCH_CHECK("k_tex_corner_uv");
   return IA_OK;
 }
@@ -208,7 +191,7 @@ extern "C" int ia_tex_texel_points(const float *verts, int nv, const int32_t *fa
   IA_CHECK_ARG(__builtin_isfinite(t_scalar), "ia_tex_texel_points: t_scalar is not finite");
   if (count == 0) return IA_OK;
   IA_CHECK_ARG(pts && (nf == 0 || faces) && (nf == 0 || nv == 0 || verts), "ia_tex_texel_points: null pointer");
-  hipLaunchKernelGGL(k_tex_texel_points, dim3(tex_blocks(count)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, verts, nv, faces, nf, B,
+  hipLaunchKernelGGL(k_tex_texel_points, dim3(ia_div_up(count, IA_TEX_THREADS)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, verts, nv, faces, nf, B,
                      T, first, count, t, t_scalar, pts, normal, owner);
   IA_LAUNCH_CHECK("k_tex_texel_points");
   return IA_OK;
@@ -223,7 +206,7 @@ extern "C" int ia_tex_snap(const float *sigma, int K, int n, float level, float 
   IA_CHECK_ARG(__builtin_isfinite(level), "ia_tex_snap: level is not finite");
   if (n == 0) return IA_OK;
   IA_CHECK_ARG(sigma && t_out && unsnapped, "ia_tex_snap: null pointer");
-  hipLaunchKernelGGL(k_tex_snap, dim3(tex_blocks(n)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, sigma, K, n, level, dist, owner,
+  hipLaunchKernelGGL(k_tex_snap, dim3(ia_div_up(n, IA_TEX_THREADS)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, sigma, K, n, level, dist, owner,
                      t_out, unsnapped);
   IA_LAUNCH_CHECK("k_tex_snap");
   return IA_OK;
@@ -234,7 +217,7 @@ extern "C" int ia_tex_sample(const float *atlas, int T, const float *uv, const f
   IA_CHECK_ARG(R >= 0, "ia_tex_sample: R = %d < 0", R);
   if (R == 0) return IA_OK;
   IA_CHECK_ARG(atlas && uv && rgb_out, "ia_tex_sample: null pointer");
-  hipLaunchKernelGGL(k_tex_sample, dim3(tex_blocks(R)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, atlas, T, uv, mask, R, rgb_out);
+  hipLaunchKernelGGL(k_tex_sample, dim3(ia_div_up(R, IA_TEX_THREADS)), dim3(IA_TEX_THREADS), 0, (hipStream_t)stream, atlas, T, uv, mask, R, rgb_out);
   IA_LAUNCH_CHECK("k_tex_sample");
   return IA_OK;
 }

@@ -132,6 +132,7 @@ def test_new_prototypes_are_declared_and_exported():
     assert os.path.normpath(_lib.MESH_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     inc = [os.path.basename(h) for h in build.includes_of(os.path.join(build.CSRC, "ia_isosurface.hip"))]
     assert "ia_mt_table.h" in inc and "ia_search_dev.h" in inc               # an edit of either rebuilds the unit
+    assert "ia_scan.h" in inc and "ia_mesh_dev.h" in inc                     # so does one of the mesh units' shared scan and face pieces
 
 
 def test_host_side_argument_checks():

@@ -1,5 +1,5 @@
 """The mesh extraction on the GPU (include/instantavatar_hip_mesh.h; DESIGN.md section 4, "isosurface"): every new entry
-point alone through the C ABI against the float64 references of tests/mesh_refs.py on lattices of 2..33 samples per axis,
+point alone through the C ABI against the float64 references of tests/mesh_refs.py on lattices of 2..65 samples per axis,
 then `AvatarModel.extract_mesh` / `pose_mesh` on the synthetic model and the extract_mesh driver.
 
 Tolerances.  Classification is exact (the reference reads the same fp32 lattice), so counts, faces and vertex order are
@@ -100,6 +100,9 @@ CASES = {
     "n3_centre":     (3, lambda: _centre(3), True, ANISO),
     "noise9_open":   (9, lambda: mr.noise_lattice(9, 1, LEVEL), False, BOX),          # cap off: an open mesh
     "noise33":       (33, lambda: mr.noise_lattice(33, 5, LEVEL), True, BOX),         # 141 workgroups: the scan over workgroup sums
+    # 1 073 workgroups: the scan carries past its first 1 024 sums, and the second sphere lies in the workgroups behind them
+    "far_spheres65": (65, lambda: np.maximum(mr.sphere_lattice(65, centre=(-0.7, -0.7, -0.7), radius=0.15),
+                                             mr.sphere_lattice(65, centre=(0.9, 0.7, 0.7), radius=0.15)).astype(np.float32), True, BOX),
 }
 _results = {}
 
@@ -135,6 +138,8 @@ def _case(name):
 @pytest.mark.parametrize("name", list(CASES))
 def test_count_and_emit_against_reference(name):
     N, _, cap, box = CASES[name]
+    if name == "far_spheres65":
+        assert (65 ** 3 + 255) // 256 > 1024                 # why 65: more workgroup sums than one trip of the scan over them takes
     sigma, (rv, rf, _), (v, f) = _case(name)
     print("%s: N %d, %d vertices, %d faces (reference %d, %d)" % (name, N, len(v), len(f), len(rv), len(rf)))
     assert (len(v), len(f)) == (len(rv), len(rf))
