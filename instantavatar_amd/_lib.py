@@ -98,6 +98,9 @@ PHOTOTEX_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_
 # and the scene-composition entry points (csrc/ia_scene.hip): `scene_declarations`
 SCENE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_scene.h")
 
+# and the ray-query entry points (csrc/ia_meshray.hip): `meshray_declarations`
+MESHRAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_meshray.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -418,6 +421,26 @@ def scene_declarations():
     return _scene_decls
 
 
+_meshray_decls = None
+
+
+def meshray_declarations():
+    """parse_header of include/instantavatar_hip_meshray.h, read once: a sixteenth table, bound in `lib()` and reachable through
+    `call` like the other fifteen; its names are disjoint from theirs."""
+    global _meshray_decls
+    if _meshray_decls is None:
+        d = _parse_file(MESHRAY_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
+                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
+                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
+                                | set(phototex_declarations()) | set(scene_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_meshray.h declares %s, which another header declares already" % ", ".join(both))
+        _meshray_decls = d
+    return _meshray_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -459,7 +482,8 @@ def lib():
                 + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()) \
                 + list(silhouette_declarations().items()) + list(masks_declarations().items()) + list(overlay_declarations().items()) \
                 + list(meshops_declarations().items()) + list(texture_declarations().items()) + list(rig_declarations().items()) \
-                + list(meshdist_declarations().items()) + list(phototex_declarations().items()) + list(scene_declarations().items()):
+                + list(meshdist_declarations().items()) + list(phototex_declarations().items()) + list(scene_declarations().items()) \
+                + list(meshray_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -547,7 +571,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h / instantavatar_hip_meshdist.h / instantavatar_hip_phototex.h / instantavatar_hip_scene.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h / instantavatar_hip_meshdist.h / instantavatar_hip_phototex.h / instantavatar_hip_scene.h / instantavatar_hip_meshray.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

@@ -1,5 +1,5 @@
-// ia_mesh_dev.h -- what the mesh units (ia_isosurface, ia_meshops, ia_meshdist, ia_texture, ia_phototex, ia_scene) share: the pieces a
-// face's validity is composed of, the fp64 face normal, the uniform grid of cells and the layout of the texture atlas.  No kernel
+// ia_mesh_dev.h -- what the mesh units (ia_isosurface, ia_meshops, ia_meshdist, ia_meshray, ia_texture, ia_phototex, ia_scene) share: the pieces a
+// face's validity is composed of, the fp64 face normal, the uniform grid of cells, the triangle grid's workspace and the layout of the texture atlas.  No kernel
 // lives here; everything has internal linkage, so every unit that includes the header compiles its own copy of what it calls.
 // The build has -ffp-contract=off: each function below is one fixed sequence of IEEE operations.
 #pragma once
@@ -87,6 +87,36 @@ inline int ia_grid_check(const char *who, const float lo[3], const float hi[3], 
   G->inv_h = inv_h;
   *cells = (long long)G->n[0] * G->n[1] * G->n[2];
   return IA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the triangle grid (ia_meshdist.hip builds it; ia_meshdist.hip and ia_meshray.hip read it)
+// ---------------------------------------------------------------------------------------------------------------------
+// the block of cells a face is listed in: per axis [cell(min corner), cell(max corner)]
+__device__ __forceinline__ void md_range(const IaGrid &G, const float p[3][3], int c0[3], int c1[3]) {
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const float a = fminf(p[0][d], fminf(p[1][d], p[2][d])), b = fmaxf(p[0][d], fmaxf(p[1][d], p[2][d]));
+    c0[d] = ia_grid_cell(a, G.lo[d], G.inv_h, G.n[d]);
+    c1[d] = ia_grid_cell(b, G.lo[d], G.inv_h, G.n[d]);
+  }
+}
+
+// the layout of its workspace: a record of three corners per face (NaN for a face that is not valid), the cells' offsets, counts and
+// block sums (workgroups of IA_MD_THREADS = ia_scan.h's), the cells' face lists
+#define IA_MD_THREADS 256
+struct MdWs { float4 *tri; int32_t *start, *cnt, *bsum, *pairs; size_t bytes; };
+inline MdWs md_carve(void *ws, int nf, long long cells, long long n_pairs) {
+  WsCarver w(ws, 0);
+  MdWs o;
+  const size_t f = (size_t)(nf > 0 ? nf : 1), c = (size_t)(cells > 0 ? cells : 1);
+  o.tri = w.take<float4>(3 * f);
+  o.start = w.take<int32_t>(c + 1);
+  o.cnt = w.take<int32_t>(c);
+  o.bsum = w.take<int32_t>((size_t)ia_div_up((long long)c, IA_MD_THREADS) + 1);
+  o.pairs = w.take<int32_t>((size_t)(n_pairs > 0 ? n_pairs : 1));
+  o.bytes = w.off;
+  return o;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

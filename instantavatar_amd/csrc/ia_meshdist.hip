@@ -23,7 +23,7 @@
 #include "ia_scan.h"
 #include "../../include/instantavatar_hip_meshdist.h"
 
-#define IA_MD_THREADS IA_SCAN_THREADS
+static_assert(IA_MD_THREADS == IA_SCAN_THREADS, "md_carve sizes the block sums for the scan's workgroups");
 
 namespace {
 
@@ -41,16 +41,7 @@ __device__ __forceinline__ bool md_face(const float *__restrict__ verts, const i
   return n[0] != 0.0 || n[1] != 0.0 || n[2] != 0.0;
 }
 
-// the block of cells of a face: per axis [cell(min corner), cell(max corner)]
-__device__ __forceinline__ void md_range(const IaGrid &G, const float p[3][3], int c0[3], int c1[3]) {
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    const float a = fminf(p[0][d], fminf(p[1][d], p[2][d])), b = fmaxf(p[0][d], fmaxf(p[1][d], p[2][d]));
-    c0[d] = ia_grid_cell(a, G.lo[d], G.inv_h, G.n[d]);
-    c1[d] = ia_grid_cell(b, G.lo[d], G.inv_h, G.n[d]);
-  }
-}
-
+// (the block of cells of a face, md_range, and the workspace's layout, md_carve, are ia_mesh_dev.h's: ia_meshray.hip reads the same grid)
 __global__ __launch_bounds__(IA_MD_THREADS) void k_md_zero64(unsigned long long *p) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = 0ull; }
 
 __global__ __launch_bounds__(IA_MD_THREADS) void k_md_count(const float *__restrict__ verts, const int32_t *__restrict__ faces, int nv, int nf,
@@ -100,20 +91,6 @@ __global__ __launch_bounds__(IA_MD_THREADS) void k_md_emit(const float *__restri
           if (at < n_pairs) pairs[at] = (int32_t)f;
         }
       }
-}
-
-struct MdWs { float4 *tri; int32_t *start, *cnt, *bsum, *pairs; size_t bytes; };
-MdWs md_carve(void *ws, int nf, long long cells, long long n_pairs) {
-  WsCarver w(ws, 0);
-  MdWs o;
-  const size_t f = (size_t)(nf > 0 ? nf : 1), c = (size_t)(cells > 0 ? cells : 1);
-  o.tri = w.take<float4>(3 * f);
-  o.start = w.take<int32_t>(c + 1);
-  o.cnt = w.take<int32_t>(c);
-  o.bsum = w.take<int32_t>((size_t)ia_div_up((long long)c, IA_MD_THREADS) + 1);
-  o.pairs = w.take<int32_t>((size_t)(n_pairs > 0 ? n_pairs : 1));
-  o.bytes = w.off;
-  return o;
 }
 
 // the size, the box and the cell edge, checked; the grid and its number of cells

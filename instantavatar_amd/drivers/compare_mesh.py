@@ -8,7 +8,9 @@ holds, for each direction, the mean, the root mean square, the median, the 95th 
 the two directions' mean UNSQUARED distances --, the Hausdorff distance of the samples, the normal consistency and one F-score per
 --tau (`meshdist.compare`; DESIGN.md section 4, "surface distance").  --out DIR writes `compare.json` with those numbers and
 `a_error.ply` / `b_error.ply`: each mesh with every vertex coloured by its distance to the other, blue (0) over green to red
-(--heat-max and more; default: the Hausdorff distance of the report)."""
+(--heat-max and more; default: the Hausdorff distance of the report).  --signed adds, per direction, on which side of the other mesh the
+samples lie ("ray queries"): the mean signed distance, its 5th and 95th percentile and the share of samples inside
+-- negative means inside the other mesh, which must be a closed surface."""
 import argparse
 import json
 import os
@@ -22,6 +24,7 @@ def main(argv=None):
     ap.add_argument("--samples", type=int, default=100000, help="surface samples per direction (0: the vertices)")
     ap.add_argument("--tau", type=float, nargs="*", default=[], metavar="T", help="distance thresholds of the F-scores")
     ap.add_argument("--heat-max", type=float, default=None, help="--out: the distance that is drawn red (default: the report's Hausdorff distance)")
+    ap.add_argument("--signed", action="store_true", help="also report the signed distances (negative: inside the other, closed, mesh)")
     ap.add_argument("--out", default="", metavar="DIR", help="write compare.json, a_error.ply and b_error.ply there")
     args = ap.parse_args(argv)
     for path in (args.a, args.b):
@@ -41,7 +44,7 @@ def main(argv=None):
     device = torch.device("cuda:0")
     load = lambda path: (Mesh.from_ply if path.lower().endswith(".ply") else Mesh.from_obj)(path, device)
     a, b = load(args.a), load(args.b)
-    report = a.compare(b, samples=args.samples, taus=args.tau)
+    report = a.compare(b, samples=args.samples, taus=args.tau, signed=True) if args.signed else a.compare(b, samples=args.samples, taus=args.tau)
     print("A = %s: %d vertices, %d faces;  B = %s: %d vertices, %d faces" % (args.a, a.verts.shape[0], a.faces.shape[0], args.b, b.verts.shape[0],
                                                                               b.faces.shape[0]))
     print("\n".join(meshdist.report_table(report)))

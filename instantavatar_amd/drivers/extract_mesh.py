@@ -37,7 +37,10 @@ the maximum and the mean distance, over all frames and vertices, between the rig
 "surface distance"; `Mesh.compare`): SAMPLES surface samples per direction (default 100 000), one `deviation:` line with the mean, the
 95th percentile and the maximum of the distances both ways in metres and in lattice spacings, and `deviation.json` with the whole
 report.  With --render it also writes `deviation_front.png`: the EXTRACTED mesh under the camera of `canonical_front.png`, every
-vertex coloured by its distance to the final mesh, blue (0) over green to red (2 lattice spacings and more).
+vertex coloured by its distance to the final mesh, blue (0) over green to red (2 lattice spacings and more).  --signed (with
+--deviation) adds on which side the processed surface lies ("ray queries"): one `bias:` line with the mean signed
+offset of the processed surface from the extracted one in metres and lattice spacings -- negative: inside, the surface shrank -- and the
+share of its samples inside, and the signed keys in `deviation.json`.
 
 --photo (with --texture BLOCK) additionally textures the mesh from the frames of a sequence (DESIGN.md section 4, "photo texture";
 `AvatarModel.bake_photo_texture`): every frame's posed mesh is rasterised for its depth map and the frame's pixels are projected
@@ -86,6 +89,7 @@ def main(argv=None):
     ap.add_argument("--fps", type=float, default=30.0, help="--rig with --poses: key frames per second of the glTF animation")
     ap.add_argument("--deviation", type=int, nargs="?", const=100000, default=None, metavar="SAMPLES", help="with --smooth / --simplify: report the "
                     "distance between the extracted and the processed mesh from SAMPLES surface samples per direction (default 100000)")
+    ap.add_argument("--signed", action="store_true", help="--deviation: also report on which side of the extracted surface the processed one lies")
     ap.add_argument("--photo", action="store_true", help="--texture: also texture the mesh from the frames of --data DIR (or, with --synthetic, "
                     "from generated frames): canonical_phototextured.{obj,mtl,png}, coverage.png")
     ap.add_argument("--photo-frames", type=int, default=8, metavar="N", help="--photo --synthetic: the number of generated frames")
@@ -97,6 +101,8 @@ def main(argv=None):
         ap.error("--deviation compares the extracted mesh with the processed one: it needs --smooth or --simplify")
     if args.deviation is not None and args.deviation < 0:
         ap.error("--deviation %d: the number of samples cannot be negative" % args.deviation)
+    if args.signed and args.deviation is None:
+        ap.error("--signed gives the deviation its sign: it needs --deviation")
     if args.photo and not args.texture:
         ap.error("--photo textures the atlas of --texture BLOCK from the frames: it needs --texture")
     if args.photo and not (args.synthetic or args.data):
@@ -154,12 +160,15 @@ def main(argv=None):
         from .. import mesh as mesh_mod, meshdist
         lo, hi = mesh_mod.field_box(model.net_coarse)
         spacing = float((hi.astype(np.float64) - lo.astype(np.float64)).max()) / (args.resolution - 1)
-        report = extracted.compare(mesh, samples=args.deviation)
+        report = extracted.compare(mesh, samples=args.deviation, signed=True) if args.signed else extracted.compare(mesh, samples=args.deviation)
         ab, ba = report["a_to_b"], report["b_to_a"]
         print("deviation: extracted -> processed mean %.3e p95 %.3e max %.3e m (%.3f / %.3f / %.3f spacings), processed -> extracted mean %.3e "
               "p95 %.3e max %.3e m (%.3f / %.3f / %.3f spacings), %d samples each way"
               % (ab["mean"], ab["p95"], ab["max"], ab["mean"] / spacing, ab["p95"] / spacing, ab["max"] / spacing, ba["mean"], ba["p95"],
                  ba["max"], ba["mean"] / spacing, ba["p95"] / spacing, ba["max"] / spacing, args.deviation))
+        if args.signed:
+            print("bias: the processed surface lies %+.3e m (%+.3f spacings) from the extracted one on average (negative: inside), "
+                  "%.1f %% of its samples inside" % (ba["signed_mean"], ba["signed_mean"] / spacing, 100.0 * ba["inside_share"]))
         report.update(resolution=args.resolution, spacing=spacing, samples=args.deviation,
                       extracted=dict(vertices=int(extracted.verts.shape[0]), faces=int(extracted.faces.shape[0])),
                       processed=dict(vertices=int(mesh.verts.shape[0]), faces=int(mesh.faces.shape[0])))

@@ -7,7 +7,8 @@ simplification"): vertex clustering with quadrics, Taubin smoothing, normals fro
 from the colour field (`texture`, `AvatarModel.bake_texture`; DESIGN.md section 4, "texture atlas"): `pose` keeps it, `smooth` and
 `simplify` return meshes without one, since the atlas belongs to the faces and positions it was baked over.  `Mesh.to_glb` writes
 the mesh, a rig (`rig.Rig`) and a pose track as one glTF binary ("rigged export").  `Mesh.distance_to` and
-`Mesh.compare` measure the distance to another mesh, `Mesh.from_ply` / `Mesh.from_obj` read the written files back (`meshdist`;
+`Mesh.compare` measure the distance to another mesh, `Mesh.raycast`, `Mesh.contains` and `Mesh.signed_distance_to` ask where a ray meets
+the mesh and on which side of it a point lies (DESIGN.md section 4, "ray queries"), `Mesh.from_ply` / `Mesh.from_obj` read the written files back (`meshdist`;
 DESIGN.md section 4, "surface distance").
 
 The level is OURS: the reference ships a marching-cubes helper it never calls, whose default level 0 is meant for signed
@@ -54,10 +55,27 @@ class Mesh:
         from . import meshdist
         return meshdist.closest(self.verts, other)
 
-    def compare(self, other, samples=100000, taus=()):
-        """`meshdist.compare(self, other, samples, taus)`: distances both ways, Chamfer, Hausdorff, normal consistency, F-scores"""
+    def compare(self, other, samples=100000, taus=(), signed=False):
+        """`meshdist.compare(self, other, samples, taus, signed)`: distances both ways, Chamfer, Hausdorff, normal consistency, F-scores;
+        signed: also on which side of the other mesh the samples lie"""
         from . import meshdist
-        return meshdist.compare(self, other, samples, taus)
+        return meshdist.compare(self, other, samples, taus, signed)
+
+    def raycast(self, origins, dirs, t_min=None, t_max=None):
+        """the first hit of the rays origins + t dirs with this mesh (`meshdist.TriangleGrid.raycast`; the grid is built for this one
+        call): a dict of t [P] (+inf: none), face [P], bary [P,3] and point [P,3]"""
+        from . import meshdist
+        return meshdist.TriangleGrid(self).raycast(origins, dirs, t_min, t_max)
+
+    def contains(self, points):
+        """[P] bool: the points inside this mesh, which must be a closed surface (`meshdist.TriangleGrid.contains`)"""
+        from . import meshdist
+        return meshdist.TriangleGrid(self).contains(points)
+
+    def signed_distance_to(self, other):
+        """`distance_to(other)` with dist negative for the vertices inside `other` (a closed surface), and `inside` [nv] bool"""
+        from . import meshdist
+        return meshdist.TriangleGrid(other).signed_distance(self.verts)
 
     @classmethod
     def from_ply(cls, path, device):

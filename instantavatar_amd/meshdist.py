@@ -8,8 +8,18 @@ follows from the two: Chamfer and Hausdorff distances, normal consistency, F-sco
 
 The result of a query is the face with the smallest (squared distance, face index) over ALL valid faces, every distance being one
 fixed fp64 expression; the grid only prunes, so the bytes of a result do not depend on the grid, and queries may be reordered freely
-(`closest(..., sort=True)` walks them along a Morton curve so that the lanes of a wave visit similar cells)."""
+(`closest(..., sort=True)` walks them along a Morton curve so that the lanes of a wave visit similar cells).
+
+Rays against the same grid (csrc/ia_meshray.hip, include/instantavatar_hip_meshray.h; DESIGN.md section 4, "ray queries"): the first
+hit, the number of faces hit, and from the count a line-of-sight test, an inside test and the sign of the distance:
+
+    r = grid.raycast(origins, dirs)              # t, face, bary, point
+    grid.occluded(a, b)                          # is the segment a -> b blocked?
+    grid.contains(points)                        # inside a closed surface (parity of three skewed rays)
+    grid.signed_distance(points)                 # `closest`, negative inside
+    compare(mesh_a, mesh_b, signed=True)         # ... and on which side the other surface lies"""
 import math
+import re
 
 import numpy as np
 import torch
@@ -24,6 +34,17 @@ PLASTIC = 1.32471795724474602596
 #: of 14 k cells the sort costs more than it saves (1.6 ms against 1.0 ms)
 SORT_FROM = 1 << 14
 SORT_FROM_CELLS = 1 << 18
+_inside_dirs = None
+
+
+def inside_dirs():
+    """[3,3] fp32: the three fixed ray directions of the inside test, as include/instantavatar_hip_meshray.h states them"""
+    global _inside_dirs
+    if _inside_dirs is None:
+        with open(_lib.MESHRAY_HEADER_PATH) as f:
+            rows = re.findall(r"#define IA_MESHRAY_INSIDE_DIR_\d (.*)", f.read())
+        _inside_dirs = np.array([[np.float32(x.strip().rstrip("f")) for x in r.split(",")] for r in rows], np.float32).reshape(3, 3)
+    return _inside_dirs
 
 
 def _mesh_arrays(mesh_or_verts, faces=None):
@@ -75,6 +96,7 @@ class TriangleGrid:
 
     def __init__(self, verts, faces=None, cell=None, box=None):
         self.verts, self.faces = _mesh_arrays(verts, faces)
+        self.faces_inside = 1 if box is None else 0         # the box below is the valid faces' own bounds: the ray walk may clip to it
         _lib.require_cuda(self.verts, self.faces)
         dev = self.verts.device
         self.nv, self.nf = int(self.verts.shape[0]), int(self.faces.shape[0])
@@ -158,6 +180,103 @@ class TriangleGrid:
                 out[k][order] = run[k]
         return out
 
+    # ---- rays (include/instantavatar_hip_meshray.h) ------------------------------------------------------------------------------
+    def _rays(self, origins, dirs, t_min, t_max):
+        _lib.require_cuda(origins, dirs)
+        o = origins.detach().reshape(-1, 3).float()
+        d = dirs.detach().to(o.device).float().expand_as(o) if dirs.dim() == 1 else dirs.detach().reshape(-1, 3).float()
+        if d.shape != o.shape:
+            raise _lib.IAError("rays: %d origins and %d directions" % (o.shape[0], d.shape[0]))
+        P = int(o.shape[0])
+
+        def rng(t):
+            if t is None or isinstance(t, torch.Tensor):
+                if t is not None and t.numel() != P:
+                    raise _lib.IAError("rays: %d origins and a range of %d values" % (P, t.numel()))
+                return None if t is None else t.detach().reshape(-1).float().to(o.device).contiguous()
+            return torch.full((P,), float(t), device=o.device)
+        return o.contiguous(), d.contiguous(), rng(t_min), rng(t_max), P
+
+    def ray_order(self, o, d):
+        """the permutation that sorts rays along the Morton curve of the point where they enter the grid's box (their origin when it
+        lies inside or the ray misses the box): neighbouring lanes then walk neighbouring cells"""
+        lo, hi = torch.as_tensor(self.lo, device=o.device), torch.as_tensor(self.hi, device=o.device)
+        ta, tb = (lo - o) / d, (hi - o) / d
+        t_in = torch.nan_to_num(torch.minimum(ta, tb), nan=-float("inf")).amax(1).clamp(min=0)
+        return self.morton_order(torch.nan_to_num(o + torch.nan_to_num(t_in, posinf=0.0)[:, None] * d, nan=0.0))
+
+    def _walk(self, name, o, d, t0, t1, P, extra, out, sort):
+        order = self.ray_order(o, d) if sort else None
+        run = out if order is None else {k: torch.empty_like(v) for k, v in out.items()}
+        take = (lambda x: x) if order is None else (lambda x: None if x is None else x[order].contiguous())
+        _lib.call(name, take(o), take(d), take(t0), take(t1), P, self.nf, *self.geo, self.n_pairs, self.ws, self.nbytes, self.faces_inside,
+                  *extra(run))
+        if order is not None:
+            for k in out:
+                out[k][order] = run[k]
+        return out
+
+    @torch.no_grad()
+    def raycast(self, origins, dirs, t_min=None, t_max=None, counters=False, sort=None):
+        """The first hit of the rays o + t d, t in [t_min, t_max] (a number, a tensor [P] or None: 0 / +inf; d is not normalised and may be
+        one direction for all): the face with the smallest (t, face index) over ALL valid faces that the ray hits, two-sided.
+        -> dict(t [P] fp32 (+inf: no hit; NaN: a ray that is not finite or whose range is not ordered), face [P] int32 (-1: none),
+        bary [P,3] fp32 = the weights of the face's corners, point [P,3] fp32 = their barycentric combination, or the origin where
+        nothing is hit) and, with counters, tests [P] int32 = ray-triangle evaluations made.  sort=True walks the rays along the
+        Morton curve of their entry points and scatters the results back; the bytes are the same either way.  None is False: the rays
+        of a camera are coherent as they come, and the sort then costs more than it saves (profiles/meshray_timing.txt).  No host read."""
+        o, d, t0, t1, P = self._rays(origins, dirs, t_min, t_max)
+        dev = o.device
+        out = dict(t=torch.empty(P, device=dev), face=torch.empty(P, dtype=torch.int32, device=dev), bary=torch.empty((P, 3), device=dev))
+        if counters:
+            out["tests"] = torch.empty(P, dtype=torch.int32, device=dev)
+        if P:
+            self._walk("ia_meshray_closest", o, d, t0, t1, P, lambda r: (r["t"], r["face"], r["bary"], r.get("tests")), out, sort)
+        hit = out["face"] >= 0
+        at = interpolate(self.verts, self.faces, out["face"], out["bary"]) if self.nf and self.nv else o
+        out["point"] = torch.where(hit[:, None], at, o)
+        return out
+
+    @torch.no_grad()
+    def count_hits(self, origins, dirs, t_min=None, t_max=None, limit=None, counters=False, sort=None):
+        """-> dict(count [P] int32 = min(limit, the number of valid faces the ray hits), each face once; -1 for a ray that is not valid)
+        and, with counters, tests [P].  limit = 1 is the any-hit query: the walk ends at the first hit it meets.  None: no limit."""
+        o, d, t0, t1, P = self._rays(origins, dirs, t_min, t_max)
+        limit = 2 ** 31 - 1 if limit is None else int(limit)
+        if limit < 1:
+            raise _lib.IAError("count_hits: limit = %d < 1" % limit)
+        out = dict(count=torch.empty(P, dtype=torch.int32, device=o.device))
+        if counters:
+            out["tests"] = torch.empty(P, dtype=torch.int32, device=o.device)
+        if P:
+            self._walk("ia_meshray_count", o, d, t0, t1, P, lambda r: (limit, r["count"], r.get("tests")), out, sort)
+        return out
+
+    def occluded(self, a, b):
+        """[P] bool: does the closed segment from a [P,3] to b [P,3] meet the mesh?  (the ray a + t (b - a), t in [0, 1], any-hit;
+        b - a is formed in fp32; a segment that is not finite is not occluded)"""
+        a = a.detach().reshape(-1, 3).float()
+        return self.count_hits(a, b.detach().reshape(-1, 3).float() - a, 0.0, 1.0, limit=1)["count"] > 0
+
+    def contains(self, points, sort=None):
+        """[P] bool: is the point inside the mesh?  Each point is the origin of three rays over [0, +inf] with the fixed directions
+        `inside_dirs()`; it is inside iff at least two of the three hit an odd number of faces.  This ASSUMES A CLOSED SURFACE (every
+        ray that enters also leaves); the orientation of the faces does not matter.  A point that is not finite is not inside."""
+        p = points.detach().reshape(-1, 3).float()
+        P = int(p.shape[0])
+        dirs = torch.as_tensor(inside_dirs(), device=p.device)
+        # sort=None: scattered origins are assumed, for which the Morton sort wins from SORT_FROM rays on, on small and large grids
+        # alike; surface samples come face by face and are coherent already (`compare` says sort=False) -- profiles/meshray_timing.txt
+        n = self.count_hits(p.repeat(3, 1), dirs.repeat_interleave(P, 0), sort=3 * P >= SORT_FROM if sort is None else sort)["count"].reshape(3, P)
+        return ((n > 0) & (n % 2 == 1)).sum(0) >= 2
+
+    def signed_distance(self, points, counters=False, sort=None):
+        """`closest` with the sign of `contains`: dist is negative inside the (closed) mesh; `inside` [P] bool is added to the dict"""
+        out = self.closest(points, counters, sort)
+        out["inside"] = self.contains(points, sort)
+        out["dist"] = torch.where(out["inside"], -out["dist"], out["dist"])
+        return out
+
 
 def closest(points, mesh_or_verts, faces=None):
     """`TriangleGrid(mesh_or_verts, faces).closest(points)`: the grid is built for this one call"""
@@ -224,7 +343,7 @@ def _unit(n):
 
 
 @torch.no_grad()
-def compare(a, b, samples=100000, taus=()):
+def compare(a, b, samples=100000, taus=(), signed=False):
     """The distance report between two meshes (Mesh or (verts, faces)).  -> dict:
       a_to_b, b_to_a   dicts of mean, rms, p50, p95, max of the distances from `samples` surface samples (`sample_surface`) of the
                        source to the other mesh; with samples = 0 from the source's finite vertices; percentile q = sorted[ceil(q n) - 1]
@@ -234,13 +353,16 @@ def compare(a, b, samples=100000, taus=()):
                        closest face; NaN with samples = 0 (a vertex has no face of its own)
       f_score          {tau: 2 P R / (P + R)}, P = share(d_ab <= tau), R = share(d_ba <= tau), 0 when both are 0
       samples          the number of points per direction: [n_a, n_b]
+    signed=True adds to each direction, from `TriangleGrid.signed_distance` (negative: the point lies inside the other mesh, which
+    must be a closed surface for this to mean anything): signed_mean, inside_share (the share of the points inside), signed_p05 and
+    signed_p95.  Every other key keeps its value bit for bit.
     The statistics are fp64 tensor operations gathered into ONE host read at the end; before it, building the two grids reads two
     numbers each and sampling reads each mesh's area."""
     va, fa = _mesh_arrays(a)
     vb, fb = _mesh_arrays(b)
     ga, gb = TriangleGrid(va, fa), TriangleGrid(vb, fb)
     taus = [float(t) for t in taus]
-    res, cons = [], []
+    res, cons, sres = [], [], []
     for (v, f, other, og) in ((va, fa, (vb, fb), gb), (vb, fb, (va, fa), ga)):
         if samples:
             s = sample_surface((v, f), samples)
@@ -249,6 +371,8 @@ def compare(a, b, samples=100000, taus=()):
             s, pts = None, v[torch.isfinite(v).all(1)]
         r = og.closest(pts)
         res.append(r["dist"].double())
+        if signed:
+            sres.append(torch.where(og.contains(pts, sort=False), -res[-1], res[-1]))
         if s is not None:
             n_src = _unit(face_normals(v, f)[1])[s["face"].long().clamp(min=0)]
             n_dst = _unit(face_normals(*other)[1])[r["face"].long().clamp(min=0)]
@@ -268,6 +392,16 @@ def compare(a, b, samples=100000, taus=()):
         p, r = packed[11 + 2 * k], packed[12 + 2 * k]
         out["f_score"][t] = 2 * p * r / (p + r) if p + r > 0 else 0.0
     out["samples"] = [int(dab.numel()), int(dba.numel())]
+    if signed:
+        def side(d):
+            n = d.numel()
+            if n == 0:
+                return torch.full((4,), float("nan"), dtype=torch.float64, device=d.device)
+            srt = torch.sort(d).values
+            return torch.stack([d.mean(), (d < 0).double().mean(), srt[percentile_index(0.05, n)], srt[percentile_index(0.95, n)]])
+        extra = torch.cat([side(d) for d in sres]).tolist()      # a second host read, only here
+        for key, vals in (("a_to_b", extra[:4]), ("b_to_a", extra[4:])):
+            out[key].update(zip(("signed_mean", "inside_share", "signed_p05", "signed_p95"), vals))
     return out
 
 
@@ -288,6 +422,9 @@ def report_table(report):
     for key, n in zip(("a_to_b", "b_to_a"), report["samples"]):
         d = report[key]
         rows.append("%-8s %12.5e %12.5e %12.5e %12.5e %12.5e %9d" % (key, d["mean"], d["rms"], d["p50"], d["p95"], d["max"], n))
+        if "signed_mean" in d:
+            rows.append("%-8s signed mean %+.5e   p05 %+.5e   p95 %+.5e   inside %.5f   (negative: inside the other mesh)"
+                        % ("", d["signed_mean"], d["signed_p05"], d["signed_p95"], d["inside_share"]))
     rows.append("chamfer (unsquared, halved) %.5e   hausdorff %.5e   normal consistency %.5f"
                 % (report["chamfer"], report["hausdorff"], report["normal_consistency"]))
     for t, f in report["f_score"].items():
