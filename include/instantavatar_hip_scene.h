@@ -15,7 +15,10 @@
  * the layers of a pixel are composited in the order of their depths.  That is exact only where the supports of the avatars along
  * the ray do not interleave (one is entirely in front of the other); where two bodies intertwine along a ray the nearer one is
  * put entirely in front.  `contested` of ia_scene_composite counts the pixels at which that may have happened.
- * LIMIT (shadows).  Only the ground receives shadows; an avatar does not shadow another avatar or itself.
+ * LIMIT (shadows).  The ground receives the avatars' shadows (ia_scene_shadow); the avatars receive each other's and their own only
+ * when ia_scene_receive is run on the layers before they are composited, and then as a multiplier on colours that already carry
+ * the lighting the avatar was captured under: one point light, no colour, nothing falls onto the background.  A receiver is one
+ * point per pixel and layer, the layer's expected depth, so LIMIT (layered compositing) holds for shadows as well.
  */
 #ifndef INSTANTAVATAR_HIP_SCENE_H
 #define INSTANTAVATAR_HIP_SCENE_H

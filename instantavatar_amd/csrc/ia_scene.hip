@@ -4,7 +4,9 @@
 //   the shade of the ground points under the avatars' light-view opacity maps (PCF)        (ia_scene_shadow)
 //   depth-ordered front-to-back compositing of K layers, the ground and a background       (ia_scene_composite)
 //   zero-fill of the integer counter                                                       (ia_scene_zero)
-// The definition -- every formula and its order of operations -- is stated in include/instantavatar_hip_scene.h and in DESIGN.md
+//   the layers shaded by the shadows the avatars cast on each other and on themselves     (ia_scene_receive)
+// The definition -- every formula and its order of operations -- is stated in include/instantavatar_hip_scene.h (ia_scene_receive:
+// include/instantavatar_hip_scene_receive.h) and in DESIGN.md
 // section 4 ("scene composition"); the library is built with -ffp-contract=off, so a fused multiply-add appears only where it is
 // spelled.  Streaming kernels, one thread per pixel, no LDS; the layer planes are [K,R], so a wave reads 64 consecutive values of a
 // plane.  Nothing here synchronises, allocates or reads on the host; no floating-point value is added atomically, so two calls give
@@ -16,6 +18,7 @@
 #include "ia_common.h"
 #include "ia_mesh_dev.h"
 #include "../../include/instantavatar_hip_scene.h"
+#include "../../include/instantavatar_hip_scene_receive.h"
 
 #define IA_SCENE_THREADS 256
 
@@ -227,6 +230,94 @@ __global__ __launch_bounds__(IA_SCENE_THREADS) void k_scene_composite(
   if (ia_lane() == 0 && b) atomicAdd(contested, __popcll(b));
 }
 
+struct SceneLight {          // the light, the clauses and the facing ramp of k_scene_receive, all fp64 (the fp32 arguments converted)
+  double L[3], near, bias_other, bias_self, cos0, dcos;      // dcos = cos1 - cos0
+};
+
+// k_scene_receive: one thread per pixel; layer j outside, caster k inside, so that nothing is indexed by a runtime k but global
+// memory (no per-layer register arrays, no scratch).  A pixel none of whose K opacities is positive -- most of a frame -- copies its
+// layers and leaves.  proj is read through a pointer indexed by k alone: wave-uniform, scalar loads.  The (2r + 1)^2 nearest taps of
+// neighbouring pixels fall on neighbouring texels of maps that stay in L2; no LDS, no atomics.
+__global__ __launch_bounds__(IA_SCENE_THREADS) void k_scene_receive(
+    const float *__restrict__ rays_o, const float *__restrict__ rays_d, int R, const float *__restrict__ c, const float *__restrict__ a,
+    const float *__restrict__ d, const float *__restrict__ nrm, const float *__restrict__ maps_a, const float *__restrict__ maps_d,
+    const float *__restrict__ proj, int K, int S, int radius, float strength, SceneLight p, float *__restrict__ c_out,
+    float *__restrict__ shade) {
+  const int r = blockIdx.x * IA_SCENE_THREADS + threadIdx.x;
+  if (r >= R) return;
+  bool any = false;
+  for (int k = 0; k < K; k++) any = any || a[(size_t)k * R + r] > 0.f;
+  if (!any) {
+    for (int k = 0; k < K; k++) {
+      const size_t at = (size_t)k * R + r;
+      shade[at] = 1.f;
+      c_out[3 * at] = c[3 * at];
+      c_out[3 * at + 1] = c[3 * at + 1];
+      c_out[3 * at + 2] = c[3 * at + 2];
+    }
+    return;
+  }
+  const size_t r3 = 3 * (size_t)r;
+  const double o[3] = {rays_o[r3], rays_o[r3 + 1], rays_o[r3 + 2]}, dir[3] = {rays_d[r3], rays_d[r3 + 1], rays_d[r3 + 2]};
+  const double hi = (double)(S - 1), taps = (double)((2 * radius + 1) * (2 * radius + 1));
+  const size_t SS = (size_t)S * S;
+  for (int j = 0; j < K; j++) {
+    const size_t at = (size_t)j * R + r;
+    const float aj = a[at], dj = d[at], c0 = c[3 * at], c1 = c[3 * at + 1], c2 = c[3 * at + 2];
+    const bool ok = aj > 0.f && scn_finite(aj) && scn_finite(dj) && scn_finite(c0) && scn_finite(c1) && scn_finite(c2);
+    float sh = 1.f;
+    if (ok) {
+      const double z = (double)dj / (double)aj;
+      const double X[3] = {o[0] + z * dir[0], o[1] + z * dir[1], o[2] + z * dir[2]};
+      const double q[3] = {X[0] - p.L[0], X[1] - p.L[1], X[2] - p.L[2]};
+      const double rho = sqrt(ia_dot3d(q, q));
+      for (int k = 0; k < K; k++) {
+        const float *M = proj + 12 * (size_t)k;
+        const double x0 = (((double)M[0] * X[0] + (double)M[1] * X[1]) + (double)M[2] * X[2]) + (double)M[3];
+        const double x1 = (((double)M[4] * X[0] + (double)M[5] * X[1]) + (double)M[6] * X[2]) + (double)M[7];
+        const double zl = (((double)M[8] * X[0] + (double)M[9] * X[1]) + (double)M[10] * X[2]) + (double)M[11];
+        float abar = 0.f;
+        if (zl > p.near) {
+          const double u = x0 / zl, v = x1 / zl;
+          if (u >= 0.0 && u <= hi && v >= 0.0 && v <= hi) {           // NaN fails
+            const float *ma = maps_a + (size_t)k * SS, *md = maps_d + (size_t)k * SS;
+            const double reach = rho - (k == j ? p.bias_self : p.bias_other);
+            double sum = 0.0;
+            for (int dy = -radius; dy <= radius; dy++) {
+              const size_t row = (size_t)(int)fmin(fmax(floor((v + (double)dy) + 0.5), 0.0), hi) * S;
+              for (int dx = -radius; dx <= radius; dx++) {
+                const size_t tap = row + (size_t)(int)fmin(fmax(floor((u + (double)dx) + 0.5), 0.0), hi);
+                const float m = ma[tap], s = md[tap];
+                const bool occludes = m > 0.f && (double)s < reach * (double)m;      // NaN: false
+                sum += occludes ? (double)m : 0.0;
+              }
+            }
+            abar = (float)(sum / taps);
+          }
+        }
+        sh = sh * (1.f - strength * abar);
+      }
+      float g = 0.f;
+      if (nrm) {
+        const float n0 = nrm[3 * at], n1 = nrm[3 * at + 1], n2 = nrm[3 * at + 2];
+        if ((n0 != 0.f || n1 != 0.f || n2 != 0.f) && scn_finite(n0) && scn_finite(n1) && scn_finite(n2)) {
+          const double n[3] = {n0, n1, n2}, l[3] = {p.L[0] - X[0], p.L[1] - X[1], p.L[2] - X[2]};
+          const double cosv = ia_dot3d(n, l) / sqrt(ia_dot3d(l, l));
+          if (cosv == cosv) {
+            const double t = (cosv - p.cos0) / p.dcos;
+            g = (float)(1.0 - fmin(fmax(t, 0.0), 1.0));
+          }
+        }
+      }
+      sh = sh * (1.f - strength * g);
+    }
+    shade[at] = sh;
+    c_out[3 * at] = ok ? c0 * sh : c0;
+    c_out[3 * at + 1] = ok ? c1 * sh : c1;
+    c_out[3 * at + 2] = ok ? c2 * sh : c2;
+  }
+}
+
 inline bool scn_finite_h(double x) { return __builtin_isfinite(x); }
 
 }  // namespace
@@ -295,6 +386,34 @@ extern "C" int ia_scene_shadow(const float *P, const float *a_g, int R, const fl
   hipLaunchKernelGGL(k_scene_shadow, dim3(ia_div_up(R, IA_SCENE_THREADS)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, P, a_g, R, maps, proj, K, S,
                      radius, strength, (double)near, shade);
   IA_LAUNCH_CHECK("k_scene_shadow");
+  return IA_OK;
+}
+
+extern "C" int ia_scene_receive(const float *rays_o, const float *rays_d, int R, const float *c, const float *a, const float *d,
+                                const float *nrm, const float *maps_a, const float *maps_d, const float *proj, int K, int S, float lx,
+                                float ly, float lz, int radius, float strength, float near, float bias_other, float bias_self, float cos0,
+                                float cos1, float *c_out, float *shade, void *stream) {
+  const char *who = "ia_scene_receive";
+  IA_CHECK_ARG(R >= 0, "%s: R = %d < 0", who, R);
+  IA_CHECK_ARG(K >= 1 && K <= IA_SCENE_MAX_LAYERS, "%s: K = %d outside [1, %d]", who, K, IA_SCENE_MAX_LAYERS);
+  IA_CHECK_ARG(S >= 1 && S <= IA_SCENE_MAX_MAP, "%s: S = %d outside [1, %d]", who, S, IA_SCENE_MAX_MAP);
+  IA_CHECK_ARG(radius >= 0 && radius <= IA_SCENE_MAX_PCF, "%s: PCF radius %d outside [0, %d]", who, radius, IA_SCENE_MAX_PCF);
+  IA_CHECK_ARG(strength >= 0.f && strength <= 1.f, "%s: strength = %g outside [0, 1]", who, (double)strength);
+  IA_CHECK_ARG(near > 0.f && scn_finite_h(near), "%s: near must be positive and finite", who);
+  IA_CHECK_ARG(bias_other >= 0.f && scn_finite_h(bias_other) && bias_self >= 0.f && scn_finite_h(bias_self),
+               "%s: the biases (%g, %g) must be finite and not negative", who, (double)bias_other, (double)bias_self);
+  IA_CHECK_ARG(cos0 >= -1.f && cos0 < cos1 && cos1 <= 1.f, "%s: the facing ramp needs -1 <= cos0 = %g < cos1 = %g <= 1", who, (double)cos0,
+               (double)cos1);
+  IA_CHECK_ARG(scn_finite_h(lx) && scn_finite_h(ly) && scn_finite_h(lz), "%s: the light is not finite", who);
+  if (R == 0) return IA_OK;
+  IA_CHECK_ARG(rays_o && rays_d && c && a && d && maps_a && maps_d && proj && c_out && shade, "%s: null pointer", who);
+  SceneLight p;
+  p.L[0] = (double)lx; p.L[1] = (double)ly; p.L[2] = (double)lz;
+  p.near = (double)near; p.bias_other = (double)bias_other; p.bias_self = (double)bias_self;
+  p.cos0 = (double)cos0; p.dcos = (double)cos1 - (double)cos0;
+  hipLaunchKernelGGL(k_scene_receive, dim3(ia_div_up(R, IA_SCENE_THREADS)), dim3(IA_SCENE_THREADS), 0, (hipStream_t)stream, rays_o, rays_d, R, c, a, d,
+                     nrm, maps_a, maps_d, proj, K, S, radius, strength, p, c_out, shade);
+  IA_LAUNCH_CHECK("k_scene_receive");
   return IA_OK;
 }
 

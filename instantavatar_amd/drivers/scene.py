@@ -4,6 +4,11 @@ DESIGN.md section 4, "scene composition").
     python -m instantavatar_amd.drivers.scene --synthetic --seeds 42 43 44 --spacing 0.9 --size 512 --max-frames 64 \\
         --ground --checker 0.5 --light -2 -4 2 --background 0.9,0.8,0.7 --out scene/out
     python -m instantavatar_amd.drivers.scene --subjects subjects.json --poses data/animation/aist_demo.npz --ground --light -2 -4 2
+    python -m instantavatar_amd.drivers.scene --synthetic --seeds 42 43 --spacing 0.6 --light -3 -1 4 --receive-shadows
+
+`--receive-shadows` (needs `--light`, not `--ground`): the avatars receive shadows too, each other's and their own
+(`scene.receive`); `--shadow-bias OTHER SELF` sets the two depth biases in metres, `--no-terminator` leaves out the attached shadow
+of surfaces that face away from the light.  One more line is printed: the share of avatar pixels that lie in shadow.
 
 `--subjects` takes the list of `animate --subjects` (ckpt, betas, gender, poses, seed, smpl_dir per entry) plus, per entry, an
 `"offset": [x, y, z]` in metres and a `"phase": frames`.  Writes `<i>.png` and `scene.gif` through `animate.write_frames`.  The
@@ -72,10 +77,17 @@ def main(argv=None):
     ap.add_argument("--light", type=float, nargs=3, metavar=("X", "Y", "Z"), help="a point light (camera frame: +y down); with --ground: shadows")
     ap.add_argument("--shadow-size", type=int, default=256)
     ap.add_argument("--shadow-strength", type=float, default=0.6)
+    ap.add_argument("--receive-shadows", action="store_true", help="the avatars receive shadows too, each other's and their own (needs --light)")
+    ap.add_argument("--shadow-bias", type=float, nargs=2, default=[0.02, 0.05], metavar=("OTHER", "SELF"),
+                    help="--receive-shadows: metres a caster must lie nearer to the light than the receiver, for another avatar and for "
+                         "the receiver's own (this project's choices, not measurements)")
+    ap.add_argument("--no-terminator", action="store_true", help="--receive-shadows: no attached shadow on surfaces that face away from the light")
     ap.add_argument("--background", metavar="FILE|R,G,B")
     ap.add_argument("--out", default="scene/out")
     ap.add_argument("--no-gif", action="store_true")
     args = ap.parse_args(argv)
+    if args.receive_shadows and args.light is None:
+        ap.error("--receive-shadows needs --light X Y Z: there is nothing to cast a shadow without a light")
     device = torch.device("cuda", torch.cuda.current_device())
     if args.subjects:
         with open(args.subjects) as f:
@@ -119,22 +131,32 @@ def main(argv=None):
     jitter = None if args.jitter_seed is None else animate.fixed_jitter(args.jitter_seed, device)
     sc = scene.Scene(models, seqs, ground=ground, light=args.light, shadow_size=args.shadow_size, shadow_strength=args.shadow_strength,
                      background=None if args.background is None else _background(args.background, H, W, device), jitter=jitter,
-                     phases=phases)
+                     phases=phases, receive=args.receive_shadows, receive_normals=not args.no_terminator, bias_other=args.shadow_bias[0],
+                     bias_self=args.shadow_bias[1])
     n = len(sc)
+    shadowed = torch.zeros(2, dtype=torch.int64, device=device)       # avatar pixels (alpha >= 0.5 in any layer), and those of them in shadow
     host = torch.empty((n, H, W, 4), dtype=torch.uint8, pin_memory=True)
     sc.render(0)                       # warm-up: workspaces, the loop-length hint
     sc.contested_total.zero_()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(n):
-        host[i].copy_(sc.render(i)["rgba8"], non_blocking=True)
+        out = sc.render(i)
+        host[i].copy_(out["rgba8"], non_blocking=True)
+        if args.receive_shadows:
+            solid = torch.stack([l[1] for l in sc.last_layers]) >= 0.5
+            shadowed += torch.stack([solid.any(0).sum(), (solid & (out["layer_shade"] < 0.99)).any(0).sum()])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     animate.write_frames(host.numpy(), args.out, gif=None if args.no_gif else "scene.gif")
     share = int(sc.contested_total) / float(max(1, n * H * W))
     print("rendered %d frames (%dx%d) of %d avatar(s)%s in %.3f s = %.1f frames/s (eager; PNG / GIF I/O excluded)"
-          % (n, W, H, len(seqs), " with ground shadows" if sc.shadows else "", dt, n / dt if dt > 0 else 0.0))
+          % (n, W, H, len(seqs), (" with ground shadows" if sc.shadows else "") + (" that receive shadows" if sc.receive else ""), dt, n / dt if dt > 0 else 0.0))
     print("contested pixels: %.4f %% of all" % (100.0 * share))
+    if args.receive_shadows:
+        pixels, dark = shadowed.tolist()        # the one read of the counters
+        print("avatar pixels in shadow: %.2f %% (shade below 0.99 in a layer with alpha >= 0.5; %d avatar pixels over %d frames)"
+              % (100.0 * dark / max(1, pixels), pixels, n))
     if share > 0:
         print("warning: at contested pixels two avatars are closer along the ray than %.2f m; layered compositing may order them wrongly there"
               % sc.contact)

@@ -9,9 +9,15 @@ Every avatar is rendered by `AvatarModel.render_image_fast` as it is, once for t
 second time from the light for its opacity, which is what no external compositing tool can get from the RGBA frames.  The layers are
 then ordered by depth per pixel and composited front to back (`composite`, a thin wrapper over the three entry points; no host read).
 
+With `receive=True` the avatars receive shadows as well, each other's and their own (`receive`, `ia_scene_receive`): the light
+render's depth sum is kept next to its opacity, and every layer's pixel -- one point, at the layer's expected depth -- is looked up in
+every avatar's light-view maps before the layers are composited.
+
 Two limits, both stated in the header: a layer is a whole avatar, so the order is exact only where the avatars do not interleave
-along a ray (`contested` counts the pixels where they may); and only the ground receives shadows.  The scene renders eagerly:
-captured graphs, frames in flight and multi-rank sharding are the single-avatar drivers' and are not used here.
+along a ray (`contested` counts the pixels where they may); and shadows are a multiplier on colours that already carry the lighting
+of the capture, from one point light, and none falls onto the background (without `receive` only the ground receives any).  The
+scene renders eagerly: captured graphs, frames in flight and multi-rank sharding are the single-avatar drivers' and are not used
+here.
 
 Colours are in the model's channel order (the (B, G, R) order of the training images, see `drivers.animate.write_frames`)."""
 import numpy as np
@@ -108,31 +114,99 @@ def light_rays(cam):
     return o, d, (cam.K @ w2c[:3, :4]).astype(np.float32)
 
 
-@torch.no_grad()
-def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None, contact=0.3):
-    """layers: a list of 1 .. 8 (rgb [..,3], alpha [..], depth [..]) of `render_image_fast` with a zero `bg_color` in the batch --
-    premultiplied colour, opacity, depth SUM -- all over the same rays rays_o, rays_d [..,3].  ground: a `Ground`; shadows: (maps
-    [K,S,S] light-view opacity, cameras: K `light_camera`s or a [K,3,4] tensor of projections, PCF radius, strength), used with a
-    ground only; background: None, a colour of three numbers, a [3] tensor or an image [..,3] over the same pixels.
-    -> dict(rgb, alpha, depth, rgba8, shade, contested) shaped like the layers; `shade` is None without a ground, `contested` a
-    device int32 scalar.  Three launches at most, a pack and a zero-fill; no host read."""
+def _projections(cams, dev):
+    """(proj [K,3,4] fp32 on the device, near) of K `light_camera`s or of a [K,3,4] tensor of projections (near = 0.05 then)"""
+    if torch.is_tensor(cams):
+        return cams.detach().float().reshape(-1, 3, 4).contiguous(), 0.05
+    return torch.as_tensor(np.stack([light_rays_projection(cm) for cm in cams]), device=dev), min(cm.near for cm in cams)
+
+
+def _receive(c, a, d, o, dr, maps_a, maps_d, cams, light, normals=None, radius=1, strength=0.6, bias_other=0.02, bias_self=0.05,
+             cos0=0.0, cos1=0.25):
+    """`receive` on the stacked layers c [K,R,3], a, d [K,R] and rays o, dr [R,3] -> (c_out [K,R,3], shade [K,R])"""
+    K, R = int(a.shape[0]), int(a.shape[1])
+    dev = a.device
+    f = lambda t: t.detach().float()
+    _lib.require_cuda(o, dr, maps_a, maps_d)
+    if o.shape[0] != R or dr.shape[0] != R:
+        raise _lib.IAError("scene.receive: %d rays for layers of %d pixels" % (o.shape[0], R))
+    maps_a, maps_d = f(maps_a).contiguous(), f(maps_d).contiguous()
+    proj, near = _projections(cams, dev)
+    if maps_a.dim() != 3 or maps_a.shape[1] != maps_a.shape[2] or maps_a.shape != maps_d.shape or maps_a.shape[0] != K \
+            or proj.shape[0] != K:
+        raise _lib.IAError("scene.receive: light-view maps %s / %s and %d light cameras for %d layers"
+                           % (tuple(maps_a.shape), tuple(maps_d.shape), proj.shape[0], K))
+    nrm = None
+    if normals is not None:
+        nrm = (torch.stack([f(n).reshape(R, 3) for n in normals]) if isinstance(normals, (list, tuple)) else f(normals).reshape(K, R, 3)).contiguous()
+        _lib.require_cuda(nrm)
+    lx, ly, lz = (float(v) for v in np.asarray(light, np.float64).reshape(3))
+    c_out, shade = torch.empty((K, R, 3), device=dev), torch.empty((K, R), device=dev)
+    _lib.call("ia_scene_receive", o, dr, R, c, a, d, nrm, maps_a, maps_d, proj, K, int(maps_a.shape[1]), lx, ly, lz, int(radius),
+              float(strength), near, float(bias_other), float(bias_self), float(cos0), float(cos1), c_out, shade)
+    return c_out, shade
+
+
+def _stack(layers, who):
+    """the layers of `composite` / `receive` -> (c [K,R,3], a [K,R], d [K,R], the pixels' shape)"""
     K = len(layers)
     if not 1 <= K <= MAX_LAYERS:
-        raise _lib.IAError("scene.composite: %d layers, 1 .. %d can be composited" % (K, MAX_LAYERS))
+        raise _lib.IAError("scene.%s: %d layers, 1 .. %d can be composited" % (who, K, MAX_LAYERS))
     shape = tuple(layers[0][1].shape)
     R = int(layers[0][1].numel())
-    dev = layers[0][1].device
     for rgb, alpha, depth in layers:
         _lib.require_cuda(rgb, alpha, depth)
         if alpha.numel() != R or depth.numel() != R or rgb.numel() != 3 * R:
-            raise _lib.IAError("scene.composite: the layers do not cover the same pixels")
+            raise _lib.IAError("scene.%s: the layers do not cover the same pixels" % who)
     f = lambda t: t.detach().float()
     c = torch.stack([f(l[0]).reshape(R, 3) for l in layers]).contiguous()
     a = torch.stack([f(l[1]).reshape(R) for l in layers]).contiguous()
     d = torch.stack([f(l[2]).reshape(R) for l in layers]).contiguous()
+    return c, a, d, shape
+
+
+@torch.no_grad()
+def receive(layers, rays_o, rays_d, maps_a, maps_d, cams, light, normals=None, radius=1, strength=0.6, bias_other=0.02, bias_self=0.05,
+            cos0=0.0, cos1=0.25):
+    """The layers of `composite` shaded by the shadows the avatars cast on each other and on themselves (`ia_scene_receive`; the
+    definition is in the header).  maps_a, maps_d [K,S,S]: avatar k from the light, its opacity and its depth SUM
+    (`Scene.light_view_maps`); cams: the K `light_camera`s or a [K,3,4] tensor of projections, as `shadows[1]` of `composite`; light:
+    the point light [3] in the rays' frame; normals: None, or per layer (a list, or one [K,..,3] tensor) the surface normals of
+    `render_image_fast(normals=True)` -- a layer whose surface faces away from the light is in its own attached shadow: the shade
+    falls from 1 to 1 - strength as the cosine between normal and light direction falls from cos1 to cos0.  radius: the PCF radius
+    0 .. 3 of nearest taps; bias_other / bias_self: metres by which a caster must lie nearer to the light than the receiver to
+    shadow it, for another avatar and for the receiver's own.
+    The bias and cosine defaults are this project's choices, not measurements: 5 cm of self-bias is roughly the thickness the
+    volumetric surface is smeared over along a light ray, which nobody has measured (tools/time_scene_receive.py prints the share of
+    lit pixels that shadow themselves at three biases, the evidence to look at).
+    -> (shaded layers: a list of (rgb * shade, alpha, depth) shaped like the input, shade [K,..]).  One launch, no host read."""
+    c, a, d, shape = _stack(layers, "receive")
+    o, dr = rays_o.detach().float().reshape(-1, 3).contiguous(), rays_d.detach().float().reshape(-1, 3).contiguous()
+    c_out, shade = _receive(c, a, d, o, dr, maps_a, maps_d, cams, light, normals, radius, strength, bias_other, bias_self, cos0, cos1)
+    shaded = [(c_out[k].reshape(layers[k][0].shape), layers[k][1], layers[k][2]) for k in range(len(layers))]
+    return shaded, shade.reshape(len(layers), *shape)
+
+
+@torch.no_grad()
+def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None, contact=0.3, receive=None):
+    """layers: a list of 1 .. 8 (rgb [..,3], alpha [..], depth [..]) of `render_image_fast` with a zero `bg_color` in the batch --
+    premultiplied colour, opacity, depth SUM -- all over the same rays rays_o, rays_d [..,3].  ground: a `Ground`; shadows: (maps
+    [K,S,S] light-view opacity, cameras: K `light_camera`s or a [K,3,4] tensor of projections, PCF radius, strength), used with a
+    ground only; background: None, a colour of three numbers, a [3] tensor or an image [..,3] over the same pixels.
+    receive: None, or a dict of the arguments of `receive` after the rays (maps_a, maps_d, cams, light and the options): the layers
+    are shaded first, then composited; None leaves every byte and every key of the result as it is without it.
+    -> dict(rgb, alpha, depth, rgba8, shade, contested) shaped like the layers; `shade` is None without a ground, `contested` a
+    device int32 scalar; with `receive` also layer_shade [K,..].  Four launches at most, a pack and a zero-fill; no host read."""
+    c, a, d, shape = _stack(layers, "composite")
+    K, R = int(a.shape[0]), int(a.shape[1])
+    dev = a.device
+    f = lambda t: t.detach().float()
+    if ground is not None or receive is not None:
+        o, dr = f(rays_o).reshape(-1, 3).contiguous(), f(rays_d).reshape(-1, 3).contiguous()
+    if receive is not None:
+        c, layer_shade = _receive(c, a, d, o, dr, **receive)
     t_g = a_g = c_g = shade = None
     if ground is not None:
-        o, dr = f(rays_o).reshape(-1, 3).contiguous(), f(rays_d).reshape(-1, 3).contiguous()
         _lib.require_cuda(o, dr)
         if o.shape[0] != R or dr.shape[0] != R:
             raise _lib.IAError("scene.composite: %d rays for layers of %d pixels" % (o.shape[0], R))
@@ -142,11 +216,7 @@ def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None
         if shadows is not None:
             maps, cams, radius, strength = shadows
             maps = f(maps).contiguous()
-            if torch.is_tensor(cams):
-                proj, near = f(cams).reshape(-1, 3, 4).contiguous(), 0.05
-            else:
-                proj = torch.as_tensor(np.stack([light_rays_projection(cm) for cm in cams]), device=dev)
-                near = min(cm.near for cm in cams)
+            proj, near = _projections(cams, dev)
             if maps.dim() != 3 or maps.shape[1] != maps.shape[2] or maps.shape[0] != proj.shape[0]:
                 raise _lib.IAError("scene.composite: %s opacity maps for %d light cameras" % (tuple(maps.shape), proj.shape[0]))
             shade = torch.empty(R, device=dev)
@@ -168,8 +238,11 @@ def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None
     _lib.call("ia_scene_composite", c, a, d, K, R, t_g, a_g, c_g, shade, bg, bg_const, float(contact), rgb, alpha, depth, contested)
     rgba8 = torch.empty((R, 4), dtype=torch.uint8, device=dev)
     _lib.call("ia_pack_rgba8", rgb, alpha, R, rgba8)
-    return dict(rgb=rgb.reshape(*shape, 3), alpha=alpha.reshape(shape), depth=depth.reshape(shape), rgba8=rgba8.reshape(*shape, 4),
-                shade=None if shade is None else shade.reshape(shape), contested=contested.reshape(()))
+    out = dict(rgb=rgb.reshape(*shape, 3), alpha=alpha.reshape(shape), depth=depth.reshape(shape), rgba8=rgba8.reshape(*shape, 4),
+               shade=None if shade is None else shade.reshape(shape), contested=contested.reshape(()))
+    if receive is not None:
+        out["layer_shade"] = layer_shade.reshape(K, *shape)
+    return out
 
 
 def light_rays_projection(cam):
@@ -188,14 +261,21 @@ class Scene:
     darkness of a full shadow; background: as `composite`; jitter: one occupancy-probe jitter for every render
     (`drivers.animate.fixed_jitter`; without it the occupancy probes, and with them the bytes, are random); phases: per avatar,
     frame i of the scene shows frame (i + phase) modulo the length of its sequence.
+    receive: the avatars receive shadows too, each other's and their own (`receive`); needs a light, not a ground; the result of
+    `render` gains `layer_shade` [K,H,W].  receive_normals: the camera renders are taken with normals=True and a surface that
+    faces away from the light is in its own attached shadow (where the deformer has a normal pass: with an `SMPLDeformer` the
+    term is left out); bias_other / bias_self: see `receive` -- the defaults are this project's choices, not measurements.
+    Without `receive` every byte of the result is what it is without these options.
 
     `render(i)`: per avatar one `render_image_fast` for the camera, with a zero `bg_color` so that the colour is premultiplied;
-    with a light and a ground one more render from the light through `_render`, which reuses the deformer and the test occupancy
-    grid the first render prepared for the frame (both depend on the pose alone, not on the rays) and of which only the opacity at
-    shadow_size^2 is kept; then `composite`.  `contested_total` (device int64) adds up the contested pixels over the calls."""
+    when `lit` (a light, and a ground or `receive`) one more render from the light through `_render`, which reuses the deformer
+    and the test occupancy grid the first render prepared for the frame (both depend on the pose alone, not on the rays) and of
+    which the opacity and the depth sum at shadow_size^2 are kept; then `composite`.  `contested_total` (device int64) adds up the
+    contested pixels over the calls."""
 
     def __init__(self, models, seqs, ground=None, light=None, shadow_size=256, background=None, jitter=None, shadow_radius=1,
-                 shadow_strength=0.6, extent=2.4, contact=0.3, phases=None):
+                 shadow_strength=0.6, extent=2.4, contact=0.3, phases=None, receive=False, receive_normals=True, bias_other=0.02,
+                 bias_self=0.05):
         if not isinstance(models, (list, tuple)):
             models = [models] * len(seqs)
         if len(models) != len(seqs) or not 1 <= len(seqs) <= MAX_LAYERS:
@@ -207,6 +287,12 @@ class Scene:
         self.models, self.seqs = list(models), list(seqs)
         self.ground, self.background, self.jitter = ground, background, jitter
         self.light = None if light is None else np.asarray(light, np.float64).reshape(3)
+        self.receive, self.bias_other, self.bias_self = bool(receive), float(bias_other), float(bias_self)
+        if self.receive and self.light is None:
+            raise _lib.IAError("scene.Scene: receive=True needs a light")
+        # the facing term needs a normal pass: the SMPL deformer declares `surface_normals` only to say that it has none
+        self._normals = [self.receive and bool(receive_normals) and hasattr(m.deformer, "surface_normals")
+                         and type(m.deformer).__name__ != "SMPLDeformer" for m in models]
         self.shadow_size, self.shadow_radius, self.shadow_strength = int(shadow_size), int(shadow_radius), float(shadow_strength)
         self.extent, self.contact = float(extent), float(contact)
         self.phases = [0] * len(seqs) if phases is None else [int(p) for p in phases]
@@ -214,12 +300,17 @@ class Scene:
         self.device = first.rays_o.device
         self._zero_bg = torch.zeros((1, self.H * self.W, 3), device=self.device)
         # the light cameras are built on the host: the root translations are read once, here
-        self._transl_host = [s.transl.double().cpu().numpy() for s in seqs] if self.shadows else None
+        self._transl_host = [s.transl.double().cpu().numpy() for s in seqs] if self.lit else None
         self.contested_total = torch.zeros((), dtype=torch.int64, device=self.device)
 
     @property
     def shadows(self):
         return self.light is not None and self.ground is not None
+
+    @property
+    def lit(self):
+        """whether the light views are rendered"""
+        return self.light is not None and (self.ground is not None or self.receive)
 
     def __len__(self):
         return max(len(s) for s in self.seqs)
@@ -228,6 +319,13 @@ class Scene:
     def light_view(self, k, idx, batch):
         """the opacity [S,S] of avatar k from the light and the light's camera; the frame must be prepared (right behind the
         avatar's `render_image_fast`)"""
+        alpha, _, cam = self.light_view_maps(k, idx, batch)
+        return alpha, cam
+
+    @torch.no_grad()
+    def light_view_maps(self, k, idx, batch):
+        """(opacity [S,S], depth SUM [S,S] in metres from the light, not divided by the opacity, the light's camera) of avatar k
+        from the light; the frame must be prepared (right behind the avatar's `render_image_fast`)"""
         S = self.shadow_size
         cam = light_camera(self.light, self._transl_host[k][idx], self.extent, S, device=self.device)
         o, d, _ = light_rays(cam)
@@ -237,26 +335,41 @@ class Scene:
         dist = float(np.linalg.norm(self._transl_host[k][idx] - self.light))
         lb.update(rays_o=t(o), rays_d=t(d), near=ones * (dist - 1), far=ones * (dist + 1))
         out, _ = self.models[k]._render(lb, eval_mode=True)
-        return out["alpha_coarse"].reshape(S, S), cam
+        return out["alpha_coarse"].reshape(S, S), out["depth_coarse"].reshape(S, S), cam
 
     @torch.no_grad()
     def render(self, i):
         size = (self.H, self.W)
         first = self.seqs[0]
-        layers, maps, cams = [], [], []
+        layers, maps, depths, cams, normals = [], [], [], [], []
         for k, (model, seq) in enumerate(zip(self.models, self.seqs)):
             idx = (int(i) + self.phases[k]) % len(seq)
             batch = seq.batch(idx)
             batch["rays_o"], batch["rays_d"] = first.rays_o, first.rays_d
             batch["bg_color"] = self._zero_bg
-            rgb, depth, alpha, _ = model.render_image_fast(batch, size, jitter=self.jitter)
+            if self._normals[k]:
+                rgb, depth, alpha, _, nrm = model.render_image_fast(batch, size, jitter=self.jitter, normals=True)
+                normals.append(nrm[0])
+            else:
+                rgb, depth, alpha, _ = model.render_image_fast(batch, size, jitter=self.jitter)
+                normals.append(None)
             layers.append((rgb[0], alpha[0], depth[0]))
-            if self.shadows:
-                m, cam = self.light_view(k, idx, batch)
+            if self.lit:
+                m, s, cam = self.light_view_maps(k, idx, batch)
                 maps.append(m)
+                depths.append(s)
                 cams.append(cam)
         shadows = (torch.stack(maps), cams, self.shadow_radius, self.shadow_strength) if self.shadows else None
+        received = None
+        if self.receive:
+            if any(n is not None for n in normals):      # a layer without a normal pass gets zero normals: no facing term
+                normals = [torch.zeros_like(layers[k][0]) if n is None else n for k, n in enumerate(normals)]
+            else:
+                normals = None
+            received = dict(maps_a=torch.stack(maps), maps_d=torch.stack(depths), cams=cams, light=self.light, normals=normals,
+                            radius=self.shadow_radius, strength=self.shadow_strength, bias_other=self.bias_other, bias_self=self.bias_self)
         out = composite(layers, first.rays_o, first.rays_d, ground=self.ground, shadows=shadows, background=self.background,
-                        contact=self.contact)
+                        contact=self.contact, receive=received)
         self.contested_total += out["contested"]
+        self.last_layers = layers      # the frame's unshaded (rgb, alpha, depth) per avatar: the driver's statistics read the opacities
         return out
