@@ -51,7 +51,8 @@ SHARED_HEADERS = [os.path.join(CSRC, "ia_common.h"), os.path.join(HERE, "..", "i
                   os.path.join(HERE, "..", "include", "instantavatar_hip_phototex.h"),
                   os.path.join(HERE, "..", "include", "instantavatar_hip_scene.h"),
                   os.path.join(HERE, "..", "include", "instantavatar_hip_meshray.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_scene_receive.h")]
+                  os.path.join(HERE, "..", "include", "instantavatar_hip_scene_receive.h"),
+                  os.path.join(HERE, "..", "include", "instantavatar_hip_render_iter.h")]
 _MARK = b"IA_SOURCE_MANIFEST="
 
 

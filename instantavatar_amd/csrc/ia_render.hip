@@ -7,6 +7,7 @@
 // models/structures/density_grid.py:95-125 (occupancy build);
 // deformers/snarf_deformer.py:95-103,127-141.
 #include "ia_common.h"
+#include "../../include/instantavatar_hip_render_iter.h"
 
 int ia_launch_field(const float *x, int V, const int32_t *n_dev, const FieldDev &F, float *rgb,
                     float *sigma, hipStream_t s, uint16_t *acts);
@@ -1147,6 +1148,41 @@ extern "C" size_t ia_render_workspace_bytes(int R, int max_batch, int n_init) {
   return render_ws_bytes(R, max_batch, n_init) + 4096;
 }
 
+// The four launches of the wave-front loop.  ia_render_test and the test-only entries ia_render_init_rays / ia_render_march_compact /
+// ia_render_composite_compact / ia_render_finalize (below) both go through them: one grid, block and template choice.
+// Upper bound for every launch: iteration 0 may have R alive rays, later ones never more than the first compaction leaves; keep R
+// (idle waves exit).
+static void launch_render_init_rays(int R, const float *near, const float *far, float *near_w, float *step, float *color, float *depth,
+                                    float *nohit, float *counter, int32_t *alive, int max_samples, RenderState *st, hipStream_t s) {
+  hipLaunchKernelGGL(k_render_init_rays, dim3(ia_div_up(R, 256)), dim3(256), 0, s, R, near, far, near_w, step, color, depth, nohit, counter,
+                     alive, max_samples, st);
+}
+static void launch_march_compact(const float *rays_o, const float *rays_d, float *near_w, const float *far, const float *step,
+                                 const int32_t *alive, int R, const uint32_t *occ_bits, int G, const float *aabb, RenderState *st,
+                                 float *s_pts, float *s_t, int32_t *ray_off, int32_t *ray_cnt, float *counter, int sample_cap,
+                                 int max_samples, int max_batch, hipStream_t s) {
+  const dim3 blk(256), gR(ia_div_up(R, 256));
+  if (G == 64 && ((size_t)occ_bits & 15) == 0)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_compact<true>), gR, blk, 0, s, rays_o, rays_d, near_w, far, step, alive, st, occ_bits,
+                       G, aabb, s_pts, s_t, ray_off, ray_cnt, counter, sample_cap, max_samples, max_batch);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_compact<false>), gR, blk, 0, s, rays_o, rays_d, near_w, far, step, alive, st, occ_bits,
+                       G, aabb, s_pts, s_t, ray_off, ray_cnt, counter, sample_cap, max_samples, max_batch);
+}
+static void launch_composite_compact(const int32_t *alive, int32_t *alive_next, RenderState *st, const int32_t *ray_off,
+                                     const int32_t *ray_cnt, const float *s_t, const float *step, const int32_t *pt_off,
+                                     const uint8_t *pt_cnt, const float *cand_rgb, const float *cand_sigma, int n_init, int R,
+                                     float *color, float *depth, float *nohit, float thresh, hipStream_t s) {
+  hipLaunchKernelGGL(k_composite_compact, dim3(ia_div_up(R, 256)), dim3(256), 0, s, alive, alive_next, st, ray_off, ray_cnt, s_t, step,
+                     pt_off, pt_cnt, cand_rgb, cand_sigma, n_init, color, depth, nohit, thresh);
+}
+static void launch_render_finalize(int R, const float *color, const float *depth, const float *nohit, const float *counter,
+                                   const float *bg, const RenderState *st_end, int max_samples, int32_t *n_alive_out, float *rgb,
+                                   float *depth_out, float *alpha, float *counter_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_render_finalize, dim3(ia_div_up(R, 256)), dim3(256), 0, s, R, color, depth, nohit, counter, bg, st_end, max_samples,
+                     n_alive_out, rgb, depth_out, alpha, counter_out);
+}
+
 extern "C" int ia_render_test(const float *rays_o, const float *rays_d, const float *near, const float *far, int R,
                               const float *bg, const uint32_t *occ_bits, int G, const float *aabb,
                               const float *voxel_J, const float *tfs, const int32_t *bone_ids, int n_init,
@@ -1171,35 +1207,78 @@ extern "C" int ia_render_test(const float *rays_o, const float *rays_d, const fl
   rw.s_pts = w.take<float>((size_t)cap * 3); rw.s_t = w.take<float>(cap);
   rw.q = carve_query(w, cap, n_init);
   rw.sample_cap = cap;
-  const dim3 blk(256), gR(ia_div_up(R, 256));
   // `resume` = number of iterations enqueued by earlier calls for this frame (0: new frame)
   const int it0 = resume;
   IA_CHECK_ARG(it0 >= 0 && it0 + n_iters < IA_RENDER_MAX_ITERS, "ia_render_test: more than %d wave-front iterations", IA_RENDER_MAX_ITERS - 1);
   if (it0 == 0)
-    hipLaunchKernelGGL(k_render_init_rays, gR, blk, 0, s, R, near, far, rw.near_w, rw.step, rw.color, rw.depth,
-                       rw.nohit, rw.counter, rw.alive_a, max_samples, rw.st);
+    launch_render_init_rays(R, near, far, rw.near_w, rw.step, rw.color, rw.depth, rw.nohit, rw.counter, rw.alive_a, max_samples, rw.st, s);
   for (int it = it0; it < it0 + n_iters; it++) {
     int32_t *cur = (it & 1) ? rw.alive_b : rw.alive_a;  // alive lists ping-pong on the absolute iteration index
     int32_t *nxt = (it & 1) ? rw.alive_a : rw.alive_b;
     RenderState *st = rw.st + it;
-    // upper bounds for the launches: iteration 0 may have R alive rays, later
-    // ones never more than the first compaction leaves; keep R (idle waves exit).
-    if (G == 64 && ((size_t)occ_bits & 15) == 0)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_compact<true>), gR, blk, 0, s, rays_o, rays_d, rw.near_w, far, rw.step, cur, st, occ_bits,
-                         G, aabb, rw.s_pts, rw.s_t, rw.ray_off, rw.ray_cnt, rw.counter, rw.sample_cap, max_samples, max_batch);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_compact<false>), gR, blk, 0, s, rays_o, rays_d, rw.near_w, far, rw.step, cur, st, occ_bits,
-                         G, aabb, rw.s_pts, rw.s_t, rw.ray_off, rw.ray_cnt, rw.counter, rw.sample_cap, max_samples, max_batch);
+    launch_march_compact(rays_o, rays_d, rw.near_w, far, rw.step, cur, R, occ_bits, G, aabb, st, rw.s_pts, rw.s_t, rw.ray_off, rw.ray_cnt,
+                         rw.counter, rw.sample_cap, max_samples, max_batch, s);
     rw.q.n_cand = &st->n_cand;  // zeroed with the record: no zero-fill launch per iteration
     rc = query_impl(rw.s_pts, cap, &st->n_samples, voxel_J, tfs, bone_ids, n_init, grid, F, rw.q, s, 0);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_composite_compact, gR, blk, 0, s, cur, nxt, st, rw.ray_off, rw.ray_cnt, rw.s_t, rw.step,
-                       rw.q.pt_off, rw.q.pt_cnt, rw.q.cand_rgb, rw.q.cand_sigma, n_init, rw.color, rw.depth, rw.nohit,
-                       0.01f);
+    launch_composite_compact(cur, nxt, st, rw.ray_off, rw.ray_cnt, rw.s_t, rw.step, rw.q.pt_off, rw.q.pt_cnt, rw.q.cand_rgb, rw.q.cand_sigma,
+                             n_init, R, rw.color, rw.depth, rw.nohit, 0.01f, s);
   }
-  hipLaunchKernelGGL(k_render_finalize, gR, blk, 0, s, R, rw.color, rw.depth, rw.nohit, rw.counter, bg,
-                     rw.st + it0 + n_iters, max_samples, n_alive_out, rgb, depth, alpha, counter);
+  launch_render_finalize(R, rw.color, rw.depth, rw.nohit, rw.counter, bg, rw.st + it0 + n_iters, max_samples, n_alive_out, rgb, depth, alpha,
+                         counter, s);
   IA_LAUNCH_CHECK("ia_render_test");
+  return IA_OK;
+}
+
+// ---- the loop's kernels alone (include/instantavatar_hip_render_iter.h; called by tests/ only): the same launches as above ----
+static_assert(sizeof(RenderState) == 8 * sizeof(int32_t), "instantavatar_hip_render_iter.h documents RenderState as eight int32");
+extern "C" int ia_render_init_rays(int R, const float *near, const float *far, float *near_w, float *step, float *color,
+                                   float *depth, float *nohit, float *counter, int32_t *alive, int max_samples, int32_t *state,
+                                   void *stream) {
+  IA_CHECK_ARG(R > 0 && max_samples > 0, "ia_render_init_rays: bad sizes");
+  IA_CHECK_ARG(near && far && near_w && step && color && depth && nohit && counter && alive && state, "ia_render_init_rays: null pointer");
+  launch_render_init_rays(R, near, far, near_w, step, color, depth, nohit, counter, alive, max_samples,
+                          reinterpret_cast<RenderState *>(state), (hipStream_t)stream);
+  IA_LAUNCH_CHECK("ia_render_init_rays");
+  return IA_OK;
+}
+
+extern "C" int ia_render_march_compact(const float *rays_o, const float *rays_d, float *near_w, const float *far, const float *step,
+                                       const int32_t *alive, int R, const uint32_t *occ_bits, int G, const float *aabb,
+                                       int32_t *state, float *s_pts, float *s_t, int32_t *ray_off, int32_t *ray_cnt,
+                                       float *counter, int sample_cap, int max_samples, int max_batch, void *stream) {
+  IA_CHECK_ARG(R > 0 && max_samples > 0 && max_batch > 0 && sample_cap >= 0, "ia_render_march_compact: bad sizes");
+  IA_CHECK_ARG(G >= 4 && G <= 256 && (G * G * G) % 64 == 0, "ia_render_march_compact: unsupported G=%d", G);
+  IA_CHECK_ARG(rays_o && rays_d && near_w && far && step && alive && occ_bits && aabb && state && s_pts && s_t && ray_off && ray_cnt &&
+               counter, "ia_render_march_compact: null pointer");
+  IA_CHECK_ARG((reinterpret_cast<uintptr_t>(occ_bits) & 3) == 0, "ia_render_march_compact: occ_bits must be 4-byte aligned");
+  launch_march_compact(rays_o, rays_d, near_w, far, step, alive, R, occ_bits, G, aabb, reinterpret_cast<RenderState *>(state), s_pts,
+                       s_t, ray_off, ray_cnt, counter, sample_cap, max_samples, max_batch, (hipStream_t)stream);
+  IA_LAUNCH_CHECK("ia_render_march_compact");
+  return IA_OK;
+}
+
+extern "C" int ia_render_composite_compact(const int32_t *alive, int32_t *alive_next, int32_t *state, const int32_t *ray_off,
+                                           const int32_t *ray_cnt, const float *s_t, const float *step, const int32_t *pt_off,
+                                           const uint8_t *pt_cnt, const float *cand_rgb, const float *cand_sigma, int n_init,
+                                           int R, float *color, float *depth, float *nohit, float thresh, void *stream) {
+  IA_CHECK_ARG(R > 0 && n_init >= 1 && n_init <= 255, "ia_render_composite_compact: bad sizes");
+  IA_CHECK_ARG(alive && alive_next && state && ray_off && ray_cnt && s_t && step && pt_off && pt_cnt && cand_rgb && cand_sigma && color &&
+               depth && nohit, "ia_render_composite_compact: null pointer");
+  launch_composite_compact(alive, alive_next, reinterpret_cast<RenderState *>(state), ray_off, ray_cnt, s_t, step, pt_off, pt_cnt,
+                           cand_rgb, cand_sigma, n_init, R, color, depth, nohit, thresh, (hipStream_t)stream);
+  IA_LAUNCH_CHECK("ia_render_composite_compact");
+  return IA_OK;
+}
+
+extern "C" int ia_render_finalize(int R, const float *color, const float *depth, const float *nohit, const float *counter,
+                                  const float *bg, const int32_t *state_end, int max_samples, int32_t *n_alive_out, float *rgb,
+                                  float *depth_out, float *alpha, float *counter_out, void *stream) {
+  IA_CHECK_ARG(R > 0 && max_samples > 0, "ia_render_finalize: bad sizes");
+  IA_CHECK_ARG(color && depth && nohit && counter && state_end && rgb && depth_out && alpha && counter_out, "ia_render_finalize: null pointer");
+  launch_render_finalize(R, color, depth, nohit, counter, bg, reinterpret_cast<const RenderState *>(state_end), max_samples, n_alive_out,
+                         rgb, depth_out, alpha, counter_out, (hipStream_t)stream);
+  IA_LAUNCH_CHECK("ia_render_finalize");
   return IA_OK;
 }
 
