@@ -15,6 +15,8 @@
  * the layers of a pixel are composited in the order of their depths.  That is exact only where the supports of the avatars along
  * the ray do not interleave (one is entirely in front of the other); where two bodies intertwine along a ray the nearer one is
  * put entirely in front.  `contested` of ia_scene_composite counts the pixels at which that may have happened.
+ * ia_scene_deep_composite (instantavatar_hip_scene_deep.h) lifts this limit for the camera view: it composites every sample of every
+ * avatar in depth order; the light views below keep it.
  * LIMIT (shadows).  The ground receives the avatars' shadows (ia_scene_shadow); the avatars receive each other's and their own only
  * when ia_scene_receive is run on the layers before they are composited, and then as a multiplier on colours that already carry
  * the lighting the avatar was captured under: one point light, no colour, nothing falls onto the background.  A receiver is one

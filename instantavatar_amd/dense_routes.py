@@ -70,6 +70,50 @@ def render_test(renderer, rays, model, bg_color):
     return _outputs(rays, color, depth, 1 - trans, "counter_coarse", counter.reshape(rays.near.shape))
 
 
+@torch.no_grad()
+def render_test_deep(renderer, rays, model, alive0, out, cols=None):
+    """The loop of `render_test` on the rays `alive0` (int64 indices into the frame's rays) that also RECORDS every sample it
+    composites: the same `ia_raymarch_test` / `ia_composite_test` calls, so retirement and the N_step schedule are `render_test`'s.
+    Before each `ia_composite_test` the block is written into slots done : done + n_step of the alive rays' columns of
+    out = dict(z, delta, sigma [S,n], rgb [S,n,3]) -- slot-major, what `ia_scene_deep_composite` reads for one list; ray alive0[j]
+    owns column cols[j] (default j).  `out` is zero-filled by the caller, so an unwritten slot has delta = 0.  A ray's slots are
+    exactly the ones its own render visits; those behind its own stop (T <= 1e-4) belong to the block it stopped in and are
+    recorded with it -- the compositor's rule "(double)T_k > 1e-4" cuts them, as `ia_composite_test` did.
+    -> (color [a0,3], depth [a0], alpha [a0]) of the rays, premultiplied, no background: what the fused render gives on them."""
+    _lib.require_cuda(rays.o, alive0, out["z"])
+    o, d, near, far = _flat_rays(rays)
+    near = near.clone()                                           # advanced in place by the marcher
+    n, dev, S = o.shape[0], o.device, renderer.MAX_SAMPLES
+    if out["z"].shape[0] != S:
+        raise _lib.IAError("dense_routes.render_test_deep: the record has %d slots, the renderer MAX_SAMPLES = %d" % (out["z"].shape[0], S))
+    color, depth, trans = torch.zeros((n, 3), device=dev), torch.zeros(n, device=dev), torch.ones(n, device=dev)
+    step = ((far - near) / S).contiguous()
+    grid = renderer.density_grid_test
+    occ = renderer._occ_desc(grid)
+    alive0 = alive0.reshape(-1).long().contiguous()
+    alive = alive0
+    col = torch.arange(alive0.numel(), device=dev) if cols is None else cols.reshape(-1).long()
+    done = 0
+    while done < S and alive.numel() > 0:
+        a = alive.numel()
+        n_step = max(min(renderer.MAX_BATCH_SIZE // a, S), 1)
+        pts = torch.empty((a, n_step, 3), device=dev)
+        delta, z = torch.empty((a, n_step), device=dev), torch.empty((a, n_step), device=dev)
+        _lib.call("ia_raymarch_test", o, d, near, far, alive, a, grid.occ_bits, occ, step, n_step, pts, delta, z)
+        rgb, sigma = _masked_field(model, pts, delta > 0, 0.0)
+        rgb, sigma = rgb.contiguous(), sigma.contiguous()
+        w = min(n_step, S - done)                                 # (the last block may reach past MAX_SAMPLES: its tail is empty)
+        out["z"][done:done + w, col] = z.t()[:w]
+        out["delta"][done:done + w, col] = delta.t()[:w]
+        out["sigma"][done:done + w, col] = sigma.t()[:w]
+        out["rgb"][done:done + w, col] = rgb.transpose(0, 1)[:w]
+        _lib.call("ia_composite_test", rgb, sigma, delta, z, alive, a, n_step, color, depth, trans, 0.01)
+        keep = (trans[alive] > 1e-4) & (z[:, -1] > 0)
+        alive, col = alive[keep], col[keep]
+        done += n_step
+    return color[alive0], depth[alive0], 1 - trans[alive0]
+
+
 def composite_train(sigma, dists):
     """training compositing: alpha = 1 - exp(-relu(sigma) dt), T = cumprod(1 - alpha + 1e-10), weights = alpha T (differentiable)"""
     alpha = 1.0 - torch.exp(-torch.relu(sigma) * dists)

@@ -10,6 +10,12 @@ DESIGN.md section 4, "scene composition").
 (`scene.receive`); `--shadow-bias OTHER SELF` sets the two depth biases in metres, `--no-terminator` leaves out the attached shadow
 of surfaces that face away from the light.  One more line is printed: the share of avatar pixels that lie in shadow.
 
+`--exact`: where two avatars share a pixel the frame is composited from every sample of every avatar in depth order, not from whole
+layers (`scene.composite_exact`; a second, host-driven pass over those pixels), so bodies that intertwine along a ray come out
+right; `--exact-ground` includes the pixels where one avatar and the ground meet.  Two more shares are printed, of the pixels that
+were recomposited (overlap) and of those where the avatars' samples really interleave, and the warning about contested pixels is
+dropped.
+
 `--subjects` takes the list of `animate --subjects` (ckpt, betas, gender, poses, seed, smpl_dir per entry) plus, per entry, an
 `"offset": [x, y, z]` in metres and a `"phase": frames`.  Writes `<i>.png` and `scene.gif` through `animate.write_frames`.  The
 scene renders eagerly on one GPU (no captured graphs, no frames in flight, no ranks)."""
@@ -82,10 +88,14 @@ def main(argv=None):
                     help="--receive-shadows: metres a caster must lie nearer to the light than the receiver, for another avatar and for "
                          "the receiver's own (this project's choices, not measurements)")
     ap.add_argument("--no-terminator", action="store_true", help="--receive-shadows: no attached shadow on surfaces that face away from the light")
+    ap.add_argument("--exact", action="store_true", help="composite every sample in depth order where avatars share a pixel (exact where they interleave)")
+    ap.add_argument("--exact-ground", action="store_true", help="--exact: also where one avatar and the ground share a pixel")
     ap.add_argument("--background", metavar="FILE|R,G,B")
     ap.add_argument("--out", default="scene/out")
     ap.add_argument("--no-gif", action="store_true")
     args = ap.parse_args(argv)
+    if args.exact_ground and not args.exact:
+        ap.error("--exact-ground needs --exact")
     if args.receive_shadows and args.light is None:
         ap.error("--receive-shadows needs --light X Y Z: there is nothing to cast a shadow without a light")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -132,9 +142,10 @@ def main(argv=None):
     sc = scene.Scene(models, seqs, ground=ground, light=args.light, shadow_size=args.shadow_size, shadow_strength=args.shadow_strength,
                      background=None if args.background is None else _background(args.background, H, W, device), jitter=jitter,
                      phases=phases, receive=args.receive_shadows, receive_normals=not args.no_terminator, bias_other=args.shadow_bias[0],
-                     bias_self=args.shadow_bias[1])
+                     bias_self=args.shadow_bias[1], exact=args.exact, exact_ground=args.exact_ground)
     n = len(sc)
     shadowed = torch.zeros(2, dtype=torch.int64, device=device)       # avatar pixels (alpha >= 0.5 in any layer), and those of them in shadow
+    deep = torch.zeros(2, dtype=torch.int64, device=device)           # --exact: recomposited pixels, and those of them that interleave
     host = torch.empty((n, H, W, 4), dtype=torch.uint8, pin_memory=True)
     sc.render(0)                       # warm-up: workspaces, the loop-length hint
     sc.contested_total.zero_()
@@ -143,6 +154,8 @@ def main(argv=None):
     for i in range(n):
         out = sc.render(i)
         host[i].copy_(out["rgba8"], non_blocking=True)
+        if args.exact:
+            deep += torch.stack([out["overlap"], out["interleaved"]])
         if args.receive_shadows:
             solid = torch.stack([l[1] for l in sc.last_layers]) >= 0.5
             shadowed += torch.stack([solid.any(0).sum(), (solid & (out["layer_shade"] < 0.99)).any(0).sum()])
@@ -157,7 +170,11 @@ def main(argv=None):
         pixels, dark = shadowed.tolist()        # the one read of the counters
         print("avatar pixels in shadow: %.2f %% (shade below 0.99 in a layer with alpha >= 0.5; %d avatar pixels over %d frames)"
               % (100.0 * dark / max(1, pixels), pixels, n))
-    if share > 0:
+    if args.exact:
+        over, inter = deep.tolist()
+        print("overlap pixels: %.4f %% of all (recomposited from the avatars' samples); interleaved pixels: %.4f %% of all"
+              % (100.0 * over / max(1, n * H * W), 100.0 * inter / max(1, n * H * W)))
+    elif share > 0:
         print("warning: at contested pixels two avatars are closer along the ray than %.2f m; layered compositing may order them wrongly there"
               % sc.contact)
     print("wrote %d frames to %s" % (n, args.out))

@@ -13,11 +13,15 @@ With `receive=True` the avatars receive shadows as well, each other's and their 
 render's depth sum is kept next to its opacity, and every layer's pixel -- one point, at the layer's expected depth -- is looked up in
 every avatar's light-view maps before the layers are composited.
 
-Two limits, both stated in the header: a layer is a whole avatar, so the order is exact only where the avatars do not interleave
-along a ray (`contested` counts the pixels where they may); and shadows are a multiplier on colours that already carry the lighting
-of the capture, from one point light, and none falls onto the background (without `receive` only the ground receives any).  The
-scene renders eagerly: captured graphs, frames in flight and multi-rank sharding are the single-avatar drivers' and are not used
-here.
+With `exact=True` the pixels that two avatars share are composited a second time from every sample of every avatar in depth order
+(`composite_exact`, `ia_scene_deep_composite`; the samples are recorded by `dense_routes.render_test_deep`, a second, host-driven
+pass over those pixels), which is exact where bodies intertwine along a ray; the result gains `overlap` and `interleaved`.
+
+Two limits, both stated in the header: a layer is a whole avatar, so without `exact` the order is exact only where the avatars do not
+interleave along a ray (`contested` counts the pixels where they may; the light views keep this limit with `exact` too); and
+shadows are a multiplier on colours that already carry the lighting of the capture, from one point light, and none falls onto the
+background (without `receive` only the ground receives any).  The scene renders eagerly: captured graphs, frames in flight and
+multi-rank sharding are the single-avatar drivers' and are not used here.
 
 Colours are in the model's channel order (the (B, G, R) order of the training images, see `drivers.animate.write_frames`)."""
 import numpy as np
@@ -188,7 +192,7 @@ def receive(layers, rays_o, rays_d, maps_a, maps_d, cams, light, normals=None, r
 
 
 @torch.no_grad()
-def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None, contact=0.3, receive=None):
+def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None, contact=0.3, receive=None, rows=None):
     """layers: a list of 1 .. 8 (rgb [..,3], alpha [..], depth [..]) of `render_image_fast` with a zero `bg_color` in the batch --
     premultiplied colour, opacity, depth SUM -- all over the same rays rays_o, rays_d [..,3].  ground: a `Ground`; shadows: (maps
     [K,S,S] light-view opacity, cameras: K `light_camera`s or a [K,3,4] tensor of projections, PCF radius, strength), used with a
@@ -196,8 +200,12 @@ def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None
     receive: None, or a dict of the arguments of `receive` after the rays (maps_a, maps_d, cams, light and the options): the layers
     are shaded first, then composited; None leaves every byte and every key of the result as it is without it.
     -> dict(rgb, alpha, depth, rgba8, shade, contested) shaped like the layers; `shade` is None without a ground, `contested` a
-    device int32 scalar; with `receive` also layer_shade [K,..].  Four launches at most, a pack and a zero-fill; no host read."""
+    device int32 scalar; with `receive` also layer_shade [K,..].  Four launches at most, a pack and a zero-fill; no host read.
+    rows: None, or a dict that receives the flat rows the result was made from -- c [K,R,3] (unshaded), a, d [K,R], factor [K,R] |
+    None (the layers' shade), ground (t_g, a_g, c_g, shade) | None, bg, bg_const: what `composite_exact` gathers the active pixels
+    from; the result does not depend on it."""
     c, a, d, shape = _stack(layers, "composite")
+    c_in, layer_shade = c, None
     K, R = int(a.shape[0]), int(a.shape[1])
     dev = a.device
     f = lambda t: t.detach().float()
@@ -242,6 +250,72 @@ def composite(layers, rays_o, rays_d, ground=None, shadows=None, background=None
                shade=None if shade is None else shade.reshape(shape), contested=contested.reshape(()))
     if receive is not None:
         out["layer_shade"] = layer_shade.reshape(K, *shape)
+    if rows is not None:
+        rows.update(c=c_in, a=a, d=d, factor=layer_shade, ground=None if t_g is None else (t_g, a_g, c_g, shade), bg=bg, bg_const=bg_const)
+    return out
+
+
+def _takes_part(c, a, d):
+    """[K,R] bool: the layers that take part in step 3 of the composite (a > 0, c, a, d finite)"""
+    return (a > 0) & torch.isfinite(a) & torch.isfinite(d) & torch.isfinite(c).all(-1)
+
+
+def active_pixels(rows, exact_ground=False):
+    """(active [n] int64 flat pixel indices, takes [K,R] bool) of the `rows` of `composite`: the pixels where at least two layers take
+    part, with `exact_ground` also those where one layer and the ground do.  One host read (the size of the set)."""
+    takes = _takes_part(rows["c"], rows["a"], rows["d"])
+    count = takes.sum(0)
+    active = count >= 2
+    if exact_ground and rows["ground"] is not None:
+        t_g, a_g, c_g, sh = rows["ground"]
+        okg = (a_g > 0) & torch.isfinite(a_g) & torch.isfinite(t_g) & torch.isfinite(sh) & torch.isfinite(c_g).all(-1)
+        active = active | ((count >= 1) & okg)
+    return torch.nonzero(active).reshape(-1), takes
+
+
+def deep_buffers(K, S, n, device, budget=8 << 30):
+    """the zero-filled sample lists of `ia_scene_deep_composite`: dict(z, delta, sigma [K,S,n], rgb [K,S,n,3]), 24 K n S bytes"""
+    need = 24 * int(K) * int(n) * int(S)
+    if need > int(budget):
+        raise _lib.IAError("scene: the sample lists of %d active pixels (%d layers x %d slots) take %d bytes, more than deep_budget = %d"
+                           % (n, K, S, need, int(budget)))
+    z = lambda *shape: torch.zeros(shape, device=device)
+    return dict(z=z(K, S, n), delta=z(K, S, n), sigma=z(K, S, n), rgb=z(K, S, n, 3))
+
+
+@torch.no_grad()
+def composite_exact(layered, deep, active, rows, thresh=0.01):
+    """The layered result of `composite` with its active pixels recomputed from every SAMPLE of every avatar (step 5 of DESIGN.md
+    section 4, "scene composition"; `ia_scene_deep_composite`, the definition is in its header): the K sample lists of a pixel --
+    `deep`: dict(z, delta, sigma [K,S,n], rgb [K,S,n,3]) over the n pixels `active` (flat int64 indices), as
+    `dense_routes.render_test_deep` records them -- are merged by depth and composited with the ground, the shade the layers
+    receive (`layer_shade` of the pixel as a colour factor) and the background of `rows` (as `composite(..., rows=...)` fills them).
+    -> a new dict: the keys of `layered`, rgb / alpha / depth of the active pixels replaced and rgba8 repacked, plus `overlap` (the
+    number of active pixels) and `interleaved` (the number of them where two avatars' composited samples really interleave), both
+    device int32.  Every other pixel keeps its bytes.  One gather per row kind, one launch, a scatter and a pack."""
+    K, S, n = (int(v) for v in deep["z"].shape)
+    dev = deep["z"].device
+    shape = tuple(layered["alpha"].shape)
+    R = int(layered["alpha"].numel())
+    if active.numel() != n or rows["a"].shape != (K, R):
+        raise _lib.IAError("scene.composite_exact: sample lists of %d layers x %d pixels for %d active pixels of %d layers" % (K, n, active.numel(), rows["a"].shape[0]))
+    factor = None if rows["factor"] is None else rows["factor"][:, active].contiguous()
+    g = (None,) * 4 if rows["ground"] is None else tuple(x[active].contiguous() for x in rows["ground"])
+    bg = rows["bg"]
+    if bg is not None and not rows["bg_const"]:
+        bg = bg.reshape(R, 3)[active].contiguous()
+    rgb_a, alpha_a, depth_a = torch.empty((n, 3), device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
+    interleaved = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.call("ia_scene_zero", interleaved, 1)
+    _lib.call("ia_scene_deep_composite", deep["z"], deep["delta"], deep["sigma"], deep["rgb"], K, S, n, factor, *g, bg, int(rows["bg_const"]),
+              float(thresh), rgb_a, alpha_a, depth_a, interleaved)
+    rgb, alpha, depth = layered["rgb"].reshape(R, 3).clone(), layered["alpha"].reshape(R).clone(), layered["depth"].reshape(R).clone()
+    rgb[active], alpha[active], depth[active] = rgb_a, alpha_a, depth_a
+    rgba8 = torch.empty((R, 4), dtype=torch.uint8, device=dev)
+    _lib.call("ia_pack_rgba8", rgb, alpha, R, rgba8)
+    out = dict(layered)
+    out.update(rgb=rgb.reshape(*shape, 3), alpha=alpha.reshape(shape), depth=depth.reshape(shape), rgba8=rgba8.reshape(*shape, 4),
+               overlap=torch.full((), n, dtype=torch.int32, device=dev), interleaved=interleaved.reshape(()))
     return out
 
 
@@ -266,6 +340,11 @@ class Scene:
     faces away from the light is in its own attached shadow (where the deformer has a normal pass: with an `SMPLDeformer` the
     term is left out); bias_other / bias_self: see `receive` -- the defaults are this project's choices, not measurements.
     Without `receive` every byte of the result is what it is without these options.
+    exact: the pixels where at least two avatars take part (exact_ground: also one avatar and the ground) are recomposited from the
+    avatars' samples in depth order (`composite_exact`); the result gains `overlap` and `interleaved` (device int32: the pixels
+    recomposited, and those of them where the avatars' composited samples really interleave).  deep_budget: the bytes the sample
+    lists may take (24 K n S for n such pixels), beyond which `render` raises; chunk: rays per call of the recording pass (it bounds
+    the transient blocks only).  Every avatar needs the same MAX_SAMPLES.  Without `exact` no byte and no key changes.
 
     `render(i)`: per avatar one `render_image_fast` for the camera, with a zero `bg_color` so that the colour is premultiplied;
     when `lit` (a light, and a ground or `receive`) one more render from the light through `_render`, which reuses the deformer
@@ -275,7 +354,7 @@ class Scene:
 
     def __init__(self, models, seqs, ground=None, light=None, shadow_size=256, background=None, jitter=None, shadow_radius=1,
                  shadow_strength=0.6, extent=2.4, contact=0.3, phases=None, receive=False, receive_normals=True, bias_other=0.02,
-                 bias_self=0.05):
+                 bias_self=0.05, exact=False, exact_ground=False, deep_budget=8 << 30, chunk=4096):
         if not isinstance(models, (list, tuple)):
             models = [models] * len(seqs)
         if len(models) != len(seqs) or not 1 <= len(seqs) <= MAX_LAYERS:
@@ -296,6 +375,7 @@ class Scene:
         self.shadow_size, self.shadow_radius, self.shadow_strength = int(shadow_size), int(shadow_radius), float(shadow_strength)
         self.extent, self.contact = float(extent), float(contact)
         self.phases = [0] * len(seqs) if phases is None else [int(p) for p in phases]
+        self.exact, self.exact_ground, self.deep_budget, self.chunk = bool(exact), bool(exact_ground), int(deep_budget), max(int(chunk), 1)
         self.H, self.W = first.H, first.W
         self.device = first.rays_o.device
         self._zero_bg = torch.zeros((1, self.H * self.W, 3), device=self.device)
@@ -342,11 +422,13 @@ class Scene:
         size = (self.H, self.W)
         first = self.seqs[0]
         layers, maps, depths, cams, normals = [], [], [], [], []
+        batches, grids = [], []
         for k, (model, seq) in enumerate(zip(self.models, self.seqs)):
             idx = (int(i) + self.phases[k]) % len(seq)
             batch = seq.batch(idx)
             batch["rays_o"], batch["rays_d"] = first.rays_o, first.rays_d
             batch["bg_color"] = self._zero_bg
+            batches.append(batch)
             if self._normals[k]:
                 rgb, depth, alpha, _, nrm = model.render_image_fast(batch, size, jitter=self.jitter, normals=True)
                 normals.append(nrm[0])
@@ -354,6 +436,9 @@ class Scene:
                 rgb, depth, alpha, _ = model.render_image_fast(batch, size, jitter=self.jitter)
                 normals.append(None)
             layers.append((rgb[0], alpha[0], depth[0]))
+            if self.exact:      # the grid this layer was rendered with: the same model may serve two avatars, and the probes may be random
+                g = model.renderer.density_grid_test
+                grids.append((g.occ_bits.clone(), g.aabb.clone(), g.density_field.clone()))
             if self.lit:
                 m, s, cam = self.light_view_maps(k, idx, batch)
                 maps.append(m)
@@ -368,8 +453,42 @@ class Scene:
                 normals = None
             received = dict(maps_a=torch.stack(maps), maps_d=torch.stack(depths), cams=cams, light=self.light, normals=normals,
                             radius=self.shadow_radius, strength=self.shadow_strength, bias_other=self.bias_other, bias_self=self.bias_self)
+        rows = {}
         out = composite(layers, first.rays_o, first.rays_d, ground=self.ground, shadows=shadows, background=self.background,
-                        contact=self.contact, receive=received)
+                        contact=self.contact, receive=received, **(dict(rows=rows) if self.exact else {}))
         self.contested_total += out["contested"]
         self.last_layers = layers      # the frame's unshaded (rgb, alpha, depth) per avatar: the driver's statistics read the opacities
+        if self.exact:
+            out = self._exact(out, rows, batches, grids)
         return out
+
+    @torch.no_grad()
+    def _exact(self, layered, rows, batches, grids):
+        """pass 2 of `render` with exact=True: the samples of every avatar on the active pixels, then `composite_exact`"""
+        from . import dense_routes
+        from .models.structures.utils import Rays
+        zero = torch.zeros((), dtype=torch.int32, device=self.device)
+        active, takes = active_pixels(rows, self.exact_ground)
+        n = int(active.numel())                                    # the host read: the scene renders eagerly
+        if n == 0:
+            return dict(layered, overlap=zero, interleaved=zero.clone())
+        K = len(self.models)
+        S = max(int(m.renderer.MAX_SAMPLES) for m in self.models)
+        deep = deep_buffers(K, S, n, self.device, self.deep_budget)
+        for k, (model, batch) in enumerate(zip(self.models, batches)):
+            if int(model.renderer.MAX_SAMPLES) != S:
+                raise _lib.IAError("scene.Scene: exact=True needs one MAX_SAMPLES for every avatar, got %d and %d" % (model.renderer.MAX_SAMPLES, S))
+            model.deformer.prepare_deformer(batch)
+            g = model.renderer.density_grid_test
+            g.occ_bits.copy_(grids[k][0])
+            g.aabb, g.density_field = grids[k][1], grids[k][2]
+            rays = Rays(o=batch["rays_o"], d=batch["rays_d"], near=batch["near"], far=batch["far"])
+            model.deformer.transform_rays_w2s(rays)
+            field = lambda x, _, model=model: model.deformer(x, model.net_coarse, True)
+            cols = torch.nonzero(takes[k][active]).reshape(-1)   # a ray with a_k = 0 has no sample at or above the threshold
+            mine = active[cols]
+            rec = {key: v[k] for key, v in deep.items()}
+            for c0 in range(0, int(mine.numel()), self.chunk):     # the chunk only bounds the transient blocks
+                dense_routes.render_test_deep(model.renderer, rays, field, mine[c0:c0 + self.chunk], rec, cols=cols[c0:c0 + self.chunk])
+        self.last_deep, self.last_active, self.last_rows = deep, active, rows      # what the frame was merged from (the tests read them)
+        return composite_exact(layered, deep, active, rows)
