@@ -110,6 +110,9 @@ RENDER_ITER_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavat
 # and the per-sample compositor of the scene composition (csrc/ia_scene_deep.hip): `scene_deep_declarations`
 SCENE_DEEP_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_scene_deep.h")
 
+# and the PNG-encoding entry points (csrc/ia_png.hip): `png_declarations`
+PNG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_png.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -512,6 +515,27 @@ def scene_deep_declarations():
     return _scene_deep_decls
 
 
+_png_decls = None
+
+
+def png_declarations():
+    """parse_header of include/instantavatar_hip_png.h, read once: a twentieth table, bound in `lib()` and reachable through
+    `call` like the other nineteen; its names are disjoint from theirs."""
+    global _png_decls
+    if _png_decls is None:
+        d = _parse_file(PNG_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
+                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
+                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
+                                | set(phototex_declarations()) | set(scene_declarations()) | set(meshray_declarations())
+                                | set(scene_receive_declarations()) | set(render_iter_declarations()) | set(scene_deep_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_png.h declares %s, which another header declares already" % ", ".join(both))
+        _png_decls = d
+    return _png_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -555,7 +579,7 @@ def lib():
                 + list(meshops_declarations().items()) + list(texture_declarations().items()) + list(rig_declarations().items()) \
                 + list(meshdist_declarations().items()) + list(phototex_declarations().items()) + list(scene_declarations().items()) \
                 + list(meshray_declarations().items()) + list(scene_receive_declarations().items()) + list(render_iter_declarations().items()) \
-                + list(scene_deep_declarations().items()):
+                + list(scene_deep_declarations().items()) + list(png_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -643,7 +667,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h / instantavatar_hip_meshdist.h / instantavatar_hip_phototex.h / instantavatar_hip_scene.h / instantavatar_hip_meshray.h / instantavatar_hip_scene_receive.h / instantavatar_hip_render_iter.h / instantavatar_hip_scene_deep.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h / instantavatar_hip_meshdist.h / instantavatar_hip_phototex.h / instantavatar_hip_scene.h / instantavatar_hip_meshray.h / instantavatar_hip_scene_receive.h / instantavatar_hip_render_iter.h / instantavatar_hip_scene_deep.h / instantavatar_hip_png.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

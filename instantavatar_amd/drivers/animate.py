@@ -114,16 +114,30 @@ def _bgra_to_rgba(f):
     return np.ascontiguousarray(np.asarray(f)[..., [2, 1, 0, 3]])
 
 
-def write_frames(frames, out_dir, gif=None, indices=None, workers=8, prefix=""):
+def write_frames(frames, out_dir, gif=None, indices=None, workers=8, prefix="", gpu_png=False):
     """8-bit [H, W, 4] frames in the MODEL's channel order -> `<i>.png` (+ optionally one GIF) with the colours the reference's
     files have.  The reference writes with cv2.imwrite (animate.py:113), which takes channel 0 as BLUE: the model's channels are
     in the (B, G, R) order of the cv2.imread training images (peoplesnapshot.py:100), so its files hold the intended colours;
     for the GIF it converts BGRA -> RGBA first (:115).  PIL takes channel 0 as RED: the same reorder serves both.
     indices: the file number of every frame (a rank of a multi-GPU job writes only the frames it rendered); PNG encoding
-    runs on `workers` threads (zlib releases the GIL).  prefix: `<prefix><i>.png` (the mesh previews)."""
+    runs on `workers` threads (zlib releases the GIL).  prefix: `<prefix><i>.png` (the mesh previews).
+    gpu_png: the opt-in route of `--gpu-png`.  `frames` is then a uint8 tensor ON THE DEVICE (or, already encoded, a
+    `png.HostStreams`): the batch is filtered and deflated there in one call with the channel swap folded into the read
+    (`png.encode(..., swap_rb=True)`), only the compressed streams are copied to the host, and the threads (at most 16) just frame
+    and write the files.  The pixels of the files are the same; their bytes are the device encoder's, not PIL's.  Returns the
+    HostStreams then (None otherwise)."""
     from concurrent.futures import ThreadPoolExecutor
-    from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
+    if gpu_png:
+        from .. import png
+        if gif:
+            raise ValueError("write_frames: the GIF is written from pixels on the host; with gpu_png=True call write_gif for it")
+        enc = frames if isinstance(frames, png.HostStreams) else png.encode(frames, swap_rb=True).to_host()
+        indices = list(range(len(enc))) if indices is None else list(indices)
+        with ThreadPoolExecutor(max_workers=max(1, min(16, workers))) as ex:
+            list(ex.map(lambda j: enc.write_png(os.path.join(out_dir, "%s%d.png" % (prefix, indices[j])), j), range(len(enc))))
+        return enc
+    from PIL import Image
     indices = list(range(len(frames))) if indices is None else list(indices)
 
     def one(job):
@@ -160,12 +174,21 @@ def pack_normals8(out, rays_d, dst_normal, dst_shaded, light=None):
     _lib.call("ia_pack_normals8", nrm, rays_d, light, nrm.numel() // 3, dst_normal, dst_shaded)
 
 
-def write_normal_frames(normal, shaded, out_dir, indices, workers=8):
+def write_normal_frames(normal, shaded, out_dir, indices, workers=8, gpu_png=False):
     """8-bit [n,H,W,4] normal / shaded images -> `normal_<i>.png`, `shaded_<i>.png`.  The channels are written as they are:
-    red / green / blue = x / y / z of (n + 1) / 2 in the camera frame (x right, y down, z away from the camera), alpha = covered."""
+    red / green / blue = x / y / z of (n + 1) / 2 in the camera frame (x right, y down, z away from the camera), alpha = covered.
+    gpu_png: `normal` and `shaded` are uint8 tensors on the device and are encoded there (no channel swap), see write_frames."""
     from concurrent.futures import ThreadPoolExecutor
-    from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
+    if gpu_png:
+        from .. import png
+        indices = list(indices)
+        for name, batch in (("normal", normal), ("shaded", shaded)):
+            enc = png.encode(batch, swap_rb=False).to_host()
+            with ThreadPoolExecutor(max_workers=max(1, min(16, workers))) as ex:
+                list(ex.map(lambda j: enc.write_png(os.path.join(out_dir, "%s_%d.png" % (name, indices[j])), j), range(len(enc))))
+        return
+    from PIL import Image
     jobs = [("normal_%d.png" % i, f) for i, f in zip(indices, normal)] + [("shaded_%d.png" % i, f) for i, f in zip(indices, shaded)]
 
     def one(job):
@@ -187,7 +210,7 @@ def _make_renderer(model, first, size, in_flight, probes, jitter, normals=False)
 
 
 def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_flight=3, jitter=None, make_renderer=None, log=print,
-                    max_buffer_bytes=1 << 30, normals=False):
+                    max_buffer_bytes=1 << 30, normals=False, gpu_png=False, apng=None):
     """animate.py:104-118 / novel_view.py:117-127 for one rank of a job of `launch.world_size` ranks.
 
     The frames of `seq` are dealt round-robin to the ranks (parallel.shard_frames; frames are independent: no data-path
@@ -199,14 +222,23 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
     frames gathered there (RCCL gather of the packed images).
     normals: the surface-normal pass is captured behind every frame and `normal_<i>.png` / `shaded_<i>.png` are written next to
     `<i>.png` (packed on the device by one more launch, copied by the same copier stream; `<i>.png` is what it is without).
+    gpu_png: the packed frames of a chunk are PNG-encoded on the device in one batch call once the chunk's render loop has been
+    synchronised (`png.encode`); only the compressed streams are copied to the host, where threads frame and write the files.  The
+    per-frame copies of raw pixels to pinned memory are not made; a GIF, when one is asked for, still is PIL's, from one copy of the
+    frames at the end.  apng: a file name (`animation.png`): rank 0 additionally writes the sequence as one animated PNG from the
+    frames' compressed streams, gathered from the ranks as they are (needs gpu_png).
     Returns a dict: frames (of the sequence), local (rendered here), render_s (this rank's render loop, I/O and graph capture
-    excluded), frames_per_sec (whole job: frames / max over ranks of render_s), incomplete (re-rendered frames)."""
+    excluded), write_s (this rank's encoding and file writing, the GIF and the animated PNG included), frames_per_sec (whole job: frames / max over ranks of render_s), incomplete (re-rendered frames)."""
     from .launch import Launch
     from ..parallel import shard_frames
     launch = launch or Launch(device=seq.rays_o.device)
     size = (seq.H, seq.W)
     dev = seq.rays_o.device
     on_gpu = dev.type == "cuda"
+    if apng and not gpu_png:
+        raise ValueError("render_sequence: apng needs gpu_png=True (the animated PNG is made of the device encoder's streams)")
+    to_host = not gpu_png         # the per-frame copies of raw pixels
+    streams = []                  # gpu_png: the HostStreams of every chunk, for the animated PNG
     mine = shard_frames(len(seq), launch.rank, launch.world_size)
     n = len(mine)
     # the packed frames stay on the device (the GIF gather travels over RCCL from there) and in pinned host memory (PNG encoding).
@@ -215,13 +247,13 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
     per_frame = seq.H * seq.W * 4 * (3 if normals else 1)
     cap = n if gif else max(1, min(n, int(max_buffer_bytes) // per_frame))
     dev_frames = torch.empty((cap, seq.H, seq.W, 4), dtype=torch.uint8, device=dev)
-    host = torch.empty((cap, seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=on_gpu)
+    host = torch.empty((cap if to_host else 0, seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=on_gpu)
     if normals:      # [0]: normal images, [1]: shaded images
         dev_extra = torch.empty((2, cap, seq.H, seq.W, 4), dtype=torch.uint8, device=dev)
-        host_extra = torch.empty((2, cap, seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=on_gpu)
+        host_extra = torch.empty((2, cap if to_host else 0, seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=on_gpu)
         rays_d_cam = seq.rays_d.reshape(-1, 3).contiguous()
     sync = torch.cuda.synchronize if on_gpu else (lambda: None)
-    render_s, redo = 0.0, []
+    render_s, write_s, redo = 0.0, 0.0, []
     if n:
         probes = [seq.batch(mine[(j * max(n // 8, 1)) % n]) for j in range(min(8, n))]   # wave-front loop length over the shard
         renderer = (make_renderer or _make_renderer)(model, seq.batch(mine[0]), size, max(1, min(in_flight, n)), probes, jitter,
@@ -229,13 +261,15 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
 
         # device -> host copies run on their own stream behind an event: a frame's stream goes straight on to its next frame
         # instead of standing still for the PCIe transfer (every frame of a chunk has its own slot: nothing is reused in flight)
-        copier = torch.cuda.Stream(device=dev) if on_gpu else None
+        copier = torch.cuda.Stream(device=dev) if (on_gpu and to_host) else None
 
         def keep(slot):
             def consume(out, k):
                 pack_rgba8(out[:4], dev_frames[slot])
                 if normals:
                     pack_normals8(out, rays_d_cam, dev_extra[0, slot], dev_extra[1, slot])
+                if not to_host:
+                    return
                 if copier is None:
                     host[slot].copy_(dev_frames[slot])
                     if normals:
@@ -267,21 +301,34 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
                     keep(c - c0)(model.render_image_fast(seq.batch(mine[c]), size, jitter=jitter, **({"normals": True} if normals else {})), 0)
                 sync()
                 redo += bad
-                if not gif:
+                t0 = time.perf_counter()
+                if gpu_png:
+                    streams.append(write_frames(dev_frames[:c1 - c0], out_dir, indices=mine[c0:c1], gpu_png=True))
+                    if normals:
+                        write_normal_frames(dev_extra[0, :c1 - c0], dev_extra[1, :c1 - c0], out_dir, mine[c0:c1], gpu_png=True)
+                elif not gif:
                     write_frames(host[:c1 - c0].numpy(), out_dir, indices=mine[c0:c1])
                     if normals:
                         write_normal_frames(host_extra[0, :c1 - c0].numpy(), host_extra[1, :c1 - c0].numpy(), out_dir, mine[c0:c1])
+                write_s += time.perf_counter() - t0
     slowest = launch.max_over_ranks(render_s)
+    t0 = time.perf_counter()
+    if apng:
+        _write_apng(streams, seq, launch, os.path.join(out_dir, apng))
     if gif:
-        write_frames(host.numpy(), out_dir, indices=mine)
-        if normals and n:
-            write_normal_frames(host_extra[0].numpy(), host_extra[1].numpy(), out_dir, mine)
+        if gpu_png:
+            host = dev_frames[:n].cpu()
+        else:
+            write_frames(host.numpy(), out_dir, indices=mine)
+            if normals and n:
+                write_normal_frames(host_extra[0].numpy(), host_extra[1].numpy(), out_dir, mine)
         parts = launch.gather_to_main(dev_frames if launch.backend == "nccl" else host)
         if launch.is_main:
             w = launch.world_size
             write_gif([parts[i % w][i // w].numpy() for i in range(len(seq))], os.path.join(out_dir, gif))
+    write_s += time.perf_counter() - t0
     launch.barrier()
-    res = dict(frames=len(seq), local=n, render_s=render_s, frames_per_sec=(len(seq) / slowest if slowest > 0 else 0.0),
+    res = dict(frames=len(seq), local=n, render_s=render_s, write_s=write_s, frames_per_sec=(len(seq) / slowest if slowest > 0 else 0.0),
                incomplete=len(redo), in_flight=in_flight, world_size=launch.world_size)
     if log is not None and launch.is_main:
         log("rendered %d frames (%dx%d) in %.3f s = %.1f frames/s (%d rank(s), %d in flight per GPU, PNG / GIF I/O and graph capture "
@@ -289,7 +336,24 @@ def render_sequence(model, seq, out_dir, gif="animation.gif", launch=None, in_fl
     return res
 
 
-def mesh_preview(model, seq, out_dir, resolution, launch=None, log=print):
+def _write_apng(streams, seq, launch, path, fps=30):
+    """the chunks' compressed streams of this rank (`png.HostStreams`, in the order of its frames) -> one animated PNG of the whole
+    sequence, written by rank 0: the ranks' payloads and stream sizes are gathered as they are (bytes, not pixels); frame i of the
+    sequence is stream i // world_size of rank i % world_size (parallel.shard_frames)"""
+    from .. import png
+    sizes = [s.offsets[j + 1] - s.offsets[j] for s in streams for j in range(len(s))]
+    payload = torch.from_numpy(np.concatenate([np.frombuffer(s.payload, np.uint8) for s in streams] or [np.zeros(0, np.uint8)]).copy())
+    parts = launch.gather_to_main(payload)
+    counts = launch.gather_to_main(torch.tensor(sizes, dtype=torch.int64))
+    if not launch.is_main:
+        return
+    w = launch.world_size
+    ranks = [png.HostStreams(p, [0] + np.cumsum(c.numpy()).tolist(), seq.H, seq.W, 4) for p, c in zip(parts, counts)]
+    with open(path, "wb") as f:
+        f.write(png.frame_apng([ranks[i % w].stream(i // w) for i in range(len(seq))], seq.H, seq.W, 4, fps=fps, loop=0))
+
+
+def mesh_preview(model, seq, out_dir, resolution, launch=None, log=print, gpu_png=False):
     """`--mesh-preview`: the canonical mesh is extracted ONCE at lattice `resolution`; every frame is then one forward skinning
     (`pose_mesh`) plus the raster launches (`Mesh.render`) under the sequence's camera, written as `mesh_<i>.png` (vertex colours,
     alpha = covered).  Frames are dealt to the ranks as render_sequence deals them.  Returns a dict like render_sequence's."""
@@ -303,13 +367,16 @@ def mesh_preview(model, seq, out_dir, resolution, launch=None, log=print):
     mesh = model.extract_mesh(resolution=resolution)
     torch.cuda.synchronize()
     extract_s = time.perf_counter() - t0
-    host = torch.empty((len(mine), seq.H, seq.W, 4), dtype=torch.uint8, pin_memory=dev.type == "cuda")
+    host = torch.empty((len(mine), seq.H, seq.W, 4), dtype=torch.uint8, **(dict(device=dev) if gpu_png else dict(pin_memory=dev.type == "cuda")))
     t0 = time.perf_counter()
     for j, i in enumerate(mine):
         host[j].copy_(model.pose_mesh(mesh, seq.batch(i, rays=False)).render(cam)["rgba8"], non_blocking=True)
     torch.cuda.synchronize()
     render_s = time.perf_counter() - t0
-    write_frames(host.numpy(), out_dir, indices=mine, prefix="mesh_")
+    if gpu_png:         # (`host` stayed on the device: it is encoded there)
+        write_frames(host, out_dir, indices=mine, prefix="mesh_", gpu_png=True)
+    else:
+        write_frames(host.numpy(), out_dir, indices=mine, prefix="mesh_")
     slowest = launch.max_over_ranks(render_s)
     launch.barrier()
     res = dict(frames=len(seq), local=len(mine), render_s=render_s, extract_s=extract_s, frames_per_sec=(len(seq) / slowest if slowest > 0 else 0.0),
@@ -321,11 +388,24 @@ def mesh_preview(model, seq, out_dir, resolution, launch=None, log=print):
     return res
 
 
+def add_png_args(ap, apng_name="animation.png"):
+    ap.add_argument("--gpu-png", action="store_true",
+                    help="encode the PNG files on the GPU (PNG filters + deflate with run-length matches and dynamic Huffman codes, "
+                         "instantavatar_amd.png): only compressed bytes are copied to the host.  Same pixels, other file bytes than PIL's")
+    ap.add_argument("--apng", action="store_true", help="also write the sequence as one lossless animated PNG (%s); needs --gpu-png" % apng_name)
+
+
+def check_png_args(ap, args):
+    if args.apng and not args.gpu_png:
+        ap.error("--apng needs --gpu-png")
+
+
 def add_launch_args(ap):
     ap.add_argument("--in-flight", type=int, default=3, help="frames in flight per GPU (captured HIP graphs replayed round-robin on their own streams)")
     ap.add_argument("--normals", action="store_true",
                     help="also write normal_<i>.png (surface normals of the posed density field, (n + 1) / 2 in the camera frame) and "
                          "shaded_<i>.png (max(0, n . l), lit from the camera) next to <i>.png; SNARF deformer only")
+    add_png_args(ap)
     ap.add_argument("--jitter-seed", type=int, default=None,
                     help="use ONE occupancy-probe jitter for all frames (drawn from this seed) instead of a fresh draw per frame "
                          "(density_grid.py:98): the files no longer depend on how many ranks rendered the sequence")
@@ -358,6 +438,7 @@ def main(argv=None):
                          "rasterise it under the same camera -> mesh_<i>.png; SNARF deformer only")
     add_launch_args(ap)
     args = ap.parse_args(argv)
+    check_png_args(ap, args)
     from .launch import Launch
     launch = Launch.from_env(who="animate")
     device = launch.device
@@ -396,13 +477,14 @@ def main(argv=None):
         if args.mesh_preview:
             if replica is not None:
                 ap.error("--mesh-preview does not combine with --subjects")
-            res = mesh_preview(model, seq, args.out, args.mesh_preview, launch=launch)
+            res = mesh_preview(model, seq, args.out, args.mesh_preview, launch=launch, gpu_png=args.gpu_png)
             if launch.is_main:
                 print("wrote %d mesh previews (%dx%d) to %s" % (res["frames"], seq.W, seq.H, args.out))
             return 0
         jitter = None if args.jitter_seed is None else fixed_jitter(args.jitter_seed, device)
         res = render_sequence(model, seq, args.out, gif=None if args.no_gif else "animation.gif", launch=replica or launch,
-                              in_flight=args.in_flight, jitter=jitter, log=None if replica else print, normals=args.normals)
+                              in_flight=args.in_flight, jitter=jitter, log=None if replica else print, normals=args.normals,
+                              gpu_png=args.gpu_png, apng="animation.png" if args.apng else None)
         if replica is not None:
             # whole-job figure of the replicas: all frames of all subjects over the slowest rank's render loop
             slowest = launch.max_over_ranks(res["render_s"])

@@ -96,7 +96,9 @@ def main(argv=None):
     ap.add_argument("--photo-res", type=int, default=256, metavar="SIZE", help="--photo --synthetic: the edge of the generated frames in pixels")
     sequence_args.add_data_arguments(ap)
     ap.add_argument("--out", default="meshes/out")
+    animate.add_png_args(ap, apng_name="posed.png, posed_shaded.png, posed_textured.png of the --render pictures")
     args = ap.parse_args(argv)
+    animate.check_png_args(ap, args)
     if args.deviation is not None and not (args.smooth or args.simplify):
         ap.error("--deviation compares the extracted mesh with the processed one: it needs --smooth or --simplify")
     if args.deviation is not None and args.deviation < 0:
@@ -255,19 +257,24 @@ def main(argv=None):
             write(posed, "posed_%d" % i)
             if cam is not None:
                 img = posed.render(cam)
-                colour.append(img["rgba8"].cpu().numpy())
-                shaded.append(img["shaded8"].cpu().numpy())
+                keep = (lambda t: t.clone()) if args.gpu_png else (lambda t: t.cpu().numpy())
+                colour.append(keep(img["rgba8"]))
+                shaded.append(keep(img["shaded8"]))
             if textured is not None:
                 posed.texture = textured.texture
                 posed.to_obj_textured(os.path.join(args.out, "posed_%d_textured.obj" % i), mtllib="canonical_textured.mtl")
                 if cam is not None:
-                    painted.append(posed.render(cam)["rgba8"].cpu().numpy())
+                    painted.append(keep(posed.render(cam)["rgba8"]))
         n = len(seq)
         if cam is not None:
-            animate.write_frames(colour, args.out, prefix="posed_")
-            animate.write_frames(shaded, args.out, prefix="posed_shaded_")
-            if textured is not None:
-                animate.write_frames(painted, args.out, prefix="posed_textured_")
+            for frames, prefix, name in ((colour, "posed_", "posed.png"), (shaded, "posed_shaded_", "posed_shaded.png")) + \
+                    (((painted, "posed_textured_", "posed_textured.png"),) if textured is not None else ()):
+                if args.gpu_png and frames:
+                    enc = animate.write_frames(torch.stack(frames), args.out, prefix=prefix, gpu_png=True)
+                    if args.apng:
+                        enc.write_apng(os.path.join(args.out, name), fps=args.fps, loop=0)
+                else:
+                    animate.write_frames(frames, args.out, prefix=prefix)
         print("posed meshes: %d frames in %.3f s (file writing included)" % (n, time.perf_counter() - t0))
         if rig is not None and n:
             print("rig: %d influences per vertex deviate from the posed meshes by at most %.3e, %.3e on average over %d frames"

@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import torch
 
-from .animate import add_launch_args, build_model, fixed_jitter, make_rays, render_sequence
+from .animate import add_launch_args, build_model, check_png_args, fixed_jitter, make_rays, render_sequence
 
 
 def rotvec_to_matrix(v):
@@ -106,6 +106,7 @@ def main(argv=None):
     ap.add_argument("--no-gif", action="store_true")
     add_launch_args(ap)
     args = ap.parse_args(argv)
+    check_png_args(ap, args)
     if not args.synthetic and not args.ckpt:
         ap.error("--ckpt is required unless --synthetic is given")
     from .launch import Launch
@@ -117,7 +118,8 @@ def main(argv=None):
         seq = RotationSequence(args.frames, betas, device, args.downscale)
         jitter = None if args.jitter_seed is None else fixed_jitter(args.jitter_seed, device)
         res = render_sequence(model, seq, args.out, gif=None if args.no_gif else "rotation.gif", launch=launch,
-                              in_flight=args.in_flight, jitter=jitter, normals=args.normals)
+                              in_flight=args.in_flight, jitter=jitter, normals=args.normals,
+                              gpu_png=args.gpu_png, apng="rotation.png" if args.apng else None)
         if launch.is_main:
             print("wrote %d frames (%dx%d) to %s" % (res["frames"], seq.W, seq.H, args.out))
     finally:

@@ -93,7 +93,9 @@ def main(argv=None):
     ap.add_argument("--background", metavar="FILE|R,G,B")
     ap.add_argument("--out", default="scene/out")
     ap.add_argument("--no-gif", action="store_true")
+    animate.add_png_args(ap, apng_name="scene.png")
     args = ap.parse_args(argv)
+    animate.check_png_args(ap, args)
     if args.exact_ground and not args.exact:
         ap.error("--exact-ground needs --exact")
     if args.receive_shadows and args.light is None:
@@ -146,14 +148,19 @@ def main(argv=None):
     n = len(sc)
     shadowed = torch.zeros(2, dtype=torch.int64, device=device)       # avatar pixels (alpha >= 0.5 in any layer), and those of them in shadow
     deep = torch.zeros(2, dtype=torch.int64, device=device)           # --exact: recomposited pixels, and those of them that interleave
-    host = torch.empty((n, H, W, 4), dtype=torch.uint8, pin_memory=True)
+    want_host = not args.gpu_png or not args.no_gif          # raw pixels on the host: PIL's PNG route, and the GIF
+    host = torch.empty((n if want_host else 0, H, W, 4), dtype=torch.uint8, pin_memory=True)
+    frames_dev = torch.empty((n, H, W, 4), dtype=torch.uint8, device=device) if args.gpu_png else None
     sc.render(0)                       # warm-up: workspaces, the loop-length hint
     sc.contested_total.zero_()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(n):
         out = sc.render(i)
-        host[i].copy_(out["rgba8"], non_blocking=True)
+        if want_host:
+            host[i].copy_(out["rgba8"], non_blocking=True)
+        if frames_dev is not None:
+            frames_dev[i].copy_(out["rgba8"])
         if args.exact:
             deep += torch.stack([out["overlap"], out["interleaved"]])
         if args.receive_shadows:
@@ -161,7 +168,14 @@ def main(argv=None):
             shadowed += torch.stack([solid.any(0).sum(), (solid & (out["layer_shade"] < 0.99)).any(0).sum()])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    animate.write_frames(host.numpy(), args.out, gif=None if args.no_gif else "scene.gif")
+    if args.gpu_png:        # one batch call on the device, only the compressed streams come over; the GIF stays PIL's
+        enc = animate.write_frames(frames_dev, args.out, gpu_png=True)
+        if args.apng:
+            enc.write_apng(os.path.join(args.out, "scene.png"), fps=30, loop=0)
+        if not args.no_gif and n:
+            animate.write_gif(host.numpy(), os.path.join(args.out, "scene.gif"))
+    else:
+        animate.write_frames(host.numpy(), args.out, gif=None if args.no_gif else "scene.gif")
     share = int(sc.contested_total) / float(max(1, n * H * W))
     print("rendered %d frames (%dx%d) of %d avatar(s)%s in %.3f s = %.1f frames/s (eager; PNG / GIF I/O excluded)"
           % (n, W, H, len(seqs), (" with ground shadows" if sc.shadows else "") + (" that receive shadows" if sc.receive else ""), dt, n / dt if dt > 0 else 0.0))
