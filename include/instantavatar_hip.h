@@ -560,7 +560,8 @@ int ia_patch_corners(const int32_t *row_mask, const int32_t *col_mask, const flo
                      int patch, float ratio_mask, int32_t *rows, int32_t *cols, void *stream);
 /* EdgeSampler's flat pixel indices (sampler.py:33-41) from the two ia_nonzero_select results and the draws [n_mask + n_edge + n_rand]:
  * out = [row_mask W + col_mask | row_edge W + col_edge | floor(u H W)], row-major; a pick from an empty mask / band (-1) falls back
- * to the uniform pixel of its own draw (the reference raises there: np.random.randint(0, 0)).                            */
+ * to the uniform pixel of its own draw (the reference raises there: np.random.randint(0, 0)).  H W <= 2^24: a larger frame is
+ * refused (the uniform pick is clamped in float32, which is exact only up to there).                                      */
 int ia_edge_indices(const int32_t *row_mask, const int32_t *col_mask, const int32_t *row_edge, const int32_t *col_edge,
                     const float *draws, int n_mask, int n_edge, int n_rand, int H, int W, int32_t *out, void *stream);
 /* near / far of a frame's n rays (peoplesnapshot.py:146-150): |transl| -/+ 1, transl: DEVICE float[3].          */
@@ -661,8 +662,10 @@ int ia_smpl_lbs_bwd(const ia_smpl_body *body, const float *betas, const float *p
  * tensors with their own learning rates (the three parameter groups of DNeRF.py:46-50), the refresh of the half-precision
  * copy of the parameters that the field kernels read (tcnn holds fp32 master weights next to its half parameters), and,
  * with `zero_grad`, the gradient zero-fill for the next step.  Arithmetic: torch/optim/adam.py `_single_tensor_adam`
- * (see csrc/ia_optim.hip); `step` is the device-resident counter of torch's capturable state, so the call can be captured
- * in a HIP graph; `lr_dev` (device scalar, optional) lets an lr scheduler reach a captured step.
+ * as torch's CPU kernels evaluate it, for any beta1 in [0, 1): w = float(1 - beta1); exp_avg' = fma(g - m, w, m) when
+ * w < 0.5, else fma(g - m, w - 1, g) (the two forms of ATen's lerp); exp_avg_sq' = fma((1 - beta2) g, g, beta2 v);
+ * p' = p + (-(lr / (1 - beta1^t)) exp_avg') / (sqrt(exp_avg_sq') / sqrt(1 - beta2^t) + eps) (see csrc/ia_optim.hip).
+ * `step` is the device-resident counter of torch's capturable state, so the call can be captured in a HIP graph; `lr_dev` (device scalar, optional) lets an lr scheduler reach a captured step.
  *   skip_in   optional device scalar: non-zero = skip this step whatever the gradients hold (candidate overflow)
  *   found_inf optional device scalar, written: 1.0 when the step was skipped, else 0.0
  *   ws        ia_adam_workspace_bytes() bytes, zero-filled ONCE by the caller, private to one stream                     */

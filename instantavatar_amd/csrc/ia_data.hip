@@ -331,6 +331,8 @@ __global__ void k_near_far(const float *__restrict__ transl, int n, float *__res
 
 // EdgeSampler's pixel indices (sampler.py:33-41): [mask picks | edge-band picks | uniform picks], flat row-major.  A pick from an
 // empty mask / band (row = col = -1 from ia_nonzero_select) falls back to a uniform pixel, floor(u H W) clamped to H W - 1.
+// The clamp is made in float: exact up to H W = 2^24 (above it (float)(H W - 1) can round UP to H W, one pixel behind the frame),
+// which ia_edge_indices therefore refuses.
 __global__ __launch_bounds__(256) void k_edge_indices(const int32_t *__restrict__ r_m, const int32_t *__restrict__ c_m,
                                                       const int32_t *__restrict__ r_e, const int32_t *__restrict__ c_e,
                                                       const float *__restrict__ draws, int n_mask, int n_edge, int n_rand, int H, int W,
@@ -349,6 +351,7 @@ extern "C" int ia_edge_indices(const int32_t *row_mask, const int32_t *col_mask,
                                const float *draws, int n_mask, int n_edge, int n_rand, int H, int W, int32_t *out, void *stream) {
   const int n = n_mask + n_edge + n_rand;
   IA_CHECK_ARG(n_mask >= 0 && n_edge >= 0 && n_rand >= 0 && H > 0 && W > 0, "ia_edge_indices: bad sizes");
+  IA_CHECK_ARG((long long)H * W <= (1ll << 24), "ia_edge_indices: %d x %d pixels: at most 2^24 (the uniform pick is clamped in float32)", H, W);
   if (n == 0) return IA_OK;
   IA_CHECK_ARG(draws && out && (n_mask == 0 || (row_mask && col_mask)) && (n_edge == 0 || (row_edge && col_edge)), "ia_edge_indices: null pointer");
   hipLaunchKernelGGL(k_edge_indices, dim3(ia_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, row_mask, col_mask, row_edge, col_edge, draws,

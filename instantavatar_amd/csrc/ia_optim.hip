@@ -15,9 +15,10 @@
 //
 // Arithmetic = torch.optim.Adam's single-tensor path (torch/optim/adam.py `_single_tensor_adam`) as its vectorised CPU
 // kernels evaluate it (FMA in lerp and addcmul), IEEE sqrt / division:
-//   m' = fma(g - m, 1 - b1, m);  v' = fma((1 - b2) g, g, b2 v);  denom = sqrt(v') / sqrt(1 - b2^t) + eps;
-//   p' = p + (-(lr / (1 - b1^t)) m') / denom
-// restated in oracle/oracle.py `adam_step` (numpy), which tests/test_cpu_oracle.py pins to torch.optim.Adam on the CPU.
+//   w = float(1 - b1);  m' = w < 0.5 ? fma(g - m, w, m) : fma(g - m, w - 1, g)   (the two forms of ATen's lerp, chosen by the weight)
+//   v' = fma((1 - b2) g, g, b2 v);  denom = sqrt(v') / sqrt(1 - b2^t) + eps;  p' = p + (-(lr / (1 - b1^t)) m') / denom
+// restated in oracle/oracle.py `adam_step` (numpy), which tests/test_cpu_oracle.py pins to torch.optim.Adam on the CPU, and in
+// tests/step_io_refs.py `adam_ref` (exact FMA), which tests/test_gpu_step_io_kernels.py compares this file with bit for bit.
 #include "ia_common.h"
 
 #define IA_ADAM_THREADS 256
@@ -34,6 +35,7 @@ struct AdamArgs {
   const float *lr_dev[IA_ADAM_MAX_TENSORS];
   double lr[IA_ADAM_MAX_TENSORS], beta1[IA_ADAM_MAX_TENSORS], beta2[IA_ADAM_MAX_TENSORS];
   float eps[IA_ADAM_MAX_TENSORS], w1[IA_ADAM_MAX_TENSORS], w2[IA_ADAM_MAX_TENSORS], b2f[IA_ADAM_MAX_TENSORS];
+  int lerp_from_end[IA_ADAM_MAX_TENSORS];  // float(1 - beta1) >= 0.5: w1 holds weight - 1 and the lerp starts from the gradient
   long long numel[IA_ADAM_MAX_TENSORS];
   int block0[IA_ADAM_MAX_TENSORS + 1];   // first workgroup of every tensor
   int n;
@@ -99,6 +101,7 @@ __global__ __launch_bounds__(IA_ADAM_THREADS) void k_adam_update(AdamArgs a, con
   // type where they are applied.  (a NaN skip flag skips too)
   const bool skip = ws->any_bad != 0u || (skip_in != nullptr && !(*skip_in == 0.f));
   const float w1 = a.w1[t], w2 = a.w2[t], b2f = a.b2f[t], eps = a.eps[t];
+  const bool from_end = a.lerp_from_end[t] != 0;      // uniform per workgroup
   __shared__ float s_sc[2];
   if (threadIdx.x == 0) {
     const double tt = (double)a.step[t][0] + 1.0;
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(IA_ADAM_THREADS) void k_adam_update(AdamArgs a, con
   __syncthreads();
   const float nss = s_sc[0], bc2s = s_sc[1];
   auto one = [&](float pi, float gi, float &mi, float &vi) -> float {
-    mi = __builtin_fmaf(gi - mi, w1, mi);               // exp_avg.lerp_(grad, 1 - beta1)
+    mi = __builtin_fmaf(gi - mi, w1, from_end ? gi : mi);   // exp_avg.lerp_(grad, 1 - beta1): weight < 0.5 from m, else (weight - 1) from g
     vi = __builtin_fmaf(w2 * gi, gi, b2f * vi);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
     const float denom = sqrtf(vi) / bc2s + eps;         // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
     return pi + (nss * mi) / denom;                     // param.addcdiv_(exp_avg, denom, value=-step_size)
@@ -153,7 +156,8 @@ __global__ __launch_bounds__(IA_ADAM_THREADS) void k_adam_update(AdamArgs a, con
 extern "C" int ia_adam_step(const ia_adam_tensor *tensors, int n_tensors, const float *skip_in, float *found_inf,
                             int zero_grad, void *ws, size_t ws_bytes, void *stream) {
   IA_CHECK_ARG(tensors && n_tensors >= 1 && n_tensors <= IA_ADAM_MAX_TENSORS, "ia_adam_step: 1..%d tensors per call", IA_ADAM_MAX_TENSORS);
-  IA_CHECK_ARG(ws && ws_bytes >= ia_adam_workspace_bytes(), "ia_adam_step: workspace too small");
+  IA_CHECK_ARG(ws, "ia_adam_step: no workspace");
+  if (ws_bytes < ia_adam_workspace_bytes()) return ia_set_error(IA_ERR_WORKSPACE, "ia_adam_step: workspace too small");
   AdamArgs a;
   memset(&a, 0, sizeof(a));
   a.n = n_tensors;
@@ -166,7 +170,11 @@ extern "C" int ia_adam_step(const ia_adam_tensor *tensors, int n_tensors, const 
     IA_CHECK_ARG(t.beta1 >= 0 && t.beta1 < 1 && t.beta2 >= 0 && t.beta2 < 1 && t.eps >= 0, "ia_adam_step: tensor %d: bad hyper-parameters", k);
     a.param[k] = t.param; a.grad[k] = t.grad; a.m[k] = t.exp_avg; a.v[k] = t.exp_avg_sq; a.shadow[k] = t.shadow;
     a.step[k] = t.step; a.lr_dev[k] = t.lr_dev; a.lr[k] = t.lr; a.beta1[k] = t.beta1; a.beta2[k] = t.beta2;
-    a.eps[k] = (float)t.eps; a.w1[k] = (float)(1.0 - t.beta1); a.w2[k] = (float)(1.0 - t.beta2); a.b2f[k] = (float)t.beta2;
+    a.eps[k] = (float)t.eps; a.w2[k] = (float)(1.0 - t.beta2); a.b2f[k] = (float)t.beta2;
+    // ATen's lerp (native/Lerp.h, cpu/LerpKernel.cpp): |weight| < 0.5 -> fma(weight, end - start, start), else fma(weight - 1, end - start, end)
+    const float weight = (float)(1.0 - t.beta1);
+    a.lerp_from_end[k] = weight >= 0.5f ? 1 : 0;
+    a.w1[k] = a.lerp_from_end[k] ? weight - 1.f : weight;
     a.numel[k] = t.numel;
     a.block0[k] = (int)blocks;
     blocks += (t.numel + IA_ADAM_PER_BLOCK - 1) / IA_ADAM_PER_BLOCK;

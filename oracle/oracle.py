@@ -625,7 +625,8 @@ def adam_step(params, grads, state, lrs, betas=(0.9, 0.99), eps=1e-15, skip=Fals
     restated from torch/optim/adam.py `_single_tensor_adam` (no weight decay, no amsgrad) in float32 with IEEE sqrt / division
     and the two fused multiply-adds of torch's vectorised CPU kernels (lerp, addcmul):
         any gradient element inf / NaN (GradScaler's check)  or  skip  ->  nothing changes, returns True
-        step += 1;  m = fma(g - m, 1 - b1, m);  v = fma((1 - b2) g, g, b2 v)
+        step += 1;  w = float32(1 - b1);  m = fma(g - m, w, m) if w < 0.5 else fma(g - m, w - 1, g)   (ATen's lerp switches form
+        at |weight| >= 0.5: native/Lerp.h, cpu/LerpKernel.cpp);  v = fma((1 - b2) g, g, b2 v)
         denom = sqrt(v) / sqrt(1 - b2^step) + eps;   p = p + (-(lr / (1 - b1^step)) m) / denom
     params / grads: lists of float32 arrays (updated in place); state: list of dicts {step, exp_avg, exp_avg_sq}; lrs: one
     learning rate per tensor (the parameter groups).  Returns found_inf."""
@@ -638,7 +639,8 @@ def adam_step(params, grads, state, lrs, betas=(0.9, 0.99), eps=1e-15, skip=Fals
         st["step"] = float(st["step"]) + 1.0
         t = st["step"]
         m, v = st["exp_avg"], st["exp_avg_sq"]
-        m[...] = _fma32(g - m, f32(1 - b1), m)
+        w = f32(1 - b1)
+        m[...] = _fma32(g - m, w, m) if w < f32(0.5) else _fma32(g - m, f32(w - f32(1)), g)
         v[...] = _fma32((f32(1 - b2) * g).astype(f32), g, (f32(b2) * v).astype(f32))
         bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
         neg_step = f32(-(float(lr) / bc1))

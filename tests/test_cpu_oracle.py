@@ -1378,6 +1378,14 @@ def test_new_entry_points_validate_arguments_before_any_launch():
     assert L.ia_patch_corners(one, one, one, 0, 64, 64, 16, C.c_float(1.0), one, one, None) == 0          # n == 0: nothing to do
     assert L.ia_near_far(None, 5, None, None, None) != 0 and b"ia_near_far" in L.ia_last_error()
     assert L.ia_near_far(None, 0, None, None, None) == 0
+    # ia_edge_indices clamps its uniform pick in float32: (float)(H W - 1) is exact up to H W = 2^24 and can round up to H W above
+    # (2^24 + 3 -> 2^24 + 4), one pixel behind the frame -- such a frame is refused, with n = 0 too (before the early return)
+    assert float(np.float32(2 ** 24 + 3)) == 2 ** 24 + 4
+    for H, W in ((4097, 4096), (1, 2 ** 24 + 1), (2 ** 24 + 4, 1), (8192, 8192)):
+        for n in (0, 4):
+            assert L.ia_edge_indices(one, one, one, one, one, n, n, n, H, W, one, None) == -1 and b"2^24" in L.ia_last_error(), (H, W, n)
+    assert L.ia_edge_indices(None, None, None, None, None, 0, 0, 0, 4096, 4096, None, None) == 0          # 2^24 pixels, nothing to do
+    assert L.ia_edge_indices(one, one, one, one, None, 4, 4, 4, 4096, 4096, one, None) == -1 and b"null pointer" in L.ia_last_error()
 
 
 def test_round3_entry_points_validate_arguments_before_any_launch():
