@@ -113,6 +113,9 @@ SCENE_DEEP_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavata
 # and the PNG-encoding entry points (csrc/ia_png.hip): `png_declarations`
 PNG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_png.h")
 
+# and the patch-loss entry points (csrc/ia_lpips.hip): `lpips_declarations`
+LPIPS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_lpips.h")
+
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -536,6 +539,28 @@ def png_declarations():
     return _png_decls
 
 
+_lpips_decls = None
+
+
+def lpips_declarations():
+    """parse_header of include/instantavatar_hip_lpips.h, read once: a twenty-first table, bound in `lib()` and reachable through
+    `call` like the other twenty; its names are disjoint from theirs."""
+    global _lpips_decls
+    if _lpips_decls is None:
+        d = _parse_file(LPIPS_HEADER_PATH)
+        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
+                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
+                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
+                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
+                                | set(phototex_declarations()) | set(scene_declarations()) | set(meshray_declarations())
+                                | set(scene_receive_declarations()) | set(render_iter_declarations()) | set(scene_deep_declarations())
+                                | set(png_declarations())))
+        if both:
+            raise ImportError("instantavatar_hip_lpips.h declares %s, which another header declares already" % ", ".join(both))
+        _lpips_decls = d
+    return _lpips_decls
+
+
 def __getattr__(name):
     if name == "EXPORTED":       # the sorted names of the declared functions
         return sorted(declarations())
@@ -579,7 +604,7 @@ def lib():
                 + list(meshops_declarations().items()) + list(texture_declarations().items()) + list(rig_declarations().items()) \
                 + list(meshdist_declarations().items()) + list(phototex_declarations().items()) + list(scene_declarations().items()) \
                 + list(meshray_declarations().items()) + list(scene_receive_declarations().items()) + list(render_iter_declarations().items()) \
-                + list(scene_deep_declarations().items()) + list(png_declarations().items()):
+                + list(scene_deep_declarations().items()) + list(png_declarations().items()) + list(lpips_declarations().items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -667,7 +692,7 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h / instantavatar_hip_meshdist.h / instantavatar_hip_phototex.h / instantavatar_hip_scene.h / instantavatar_hip_meshray.h / instantavatar_hip_scene_receive.h / instantavatar_hip_render_iter.h / instantavatar_hip_scene_deep.h / instantavatar_hip_png.h)" % name)
+            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h / instantavatar_hip_meshdist.h / instantavatar_hip_phototex.h / instantavatar_hip_scene.h / instantavatar_hip_meshray.h / instantavatar_hip_scene_receive.h / instantavatar_hip_render_iter.h / instantavatar_hip_scene_deep.h / instantavatar_hip_png.h / instantavatar_hip_lpips.h)" % name)
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

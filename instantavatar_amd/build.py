@@ -22,7 +22,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libinstantavatar_hip.so")
-SOURCES = ["ia_error.cpp", "ia_snarf.hip", "ia_search.hip", "ia_field.hip", "ia_render.hip", "ia_prof.hip", "ia_voxelise.hip", "ia_loss.hip", "ia_smpl_nn.hip", "ia_data.hip", "ia_mesh.hip", "ia_optim.hip", "ia_smpl_lbs.hip", "ia_io.hip", "ia_normals.hip", "ia_isosurface.hip", "ia_raster.hip", "ia_keypoints.hip", "ia_silhouette.hip", "ia_masks.hip", "ia_overlay.hip", "ia_meshops.hip", "ia_texture.hip", "ia_rig.hip", "ia_meshdist.hip", "ia_phototex.hip", "ia_scene.hip", "ia_meshray.hip", "ia_scene_deep.hip", "ia_png.hip"]
+SOURCES = ["ia_error.cpp", "ia_snarf.hip", "ia_search.hip", "ia_field.hip", "ia_render.hip", "ia_prof.hip", "ia_voxelise.hip", "ia_loss.hip", "ia_smpl_nn.hip", "ia_data.hip", "ia_mesh.hip", "ia_optim.hip", "ia_smpl_lbs.hip", "ia_io.hip", "ia_normals.hip", "ia_isosurface.hip", "ia_raster.hip", "ia_keypoints.hip", "ia_silhouette.hip", "ia_masks.hip", "ia_overlay.hip", "ia_meshops.hip", "ia_texture.hip", "ia_rig.hip", "ia_meshdist.hip", "ia_phototex.hip", "ia_scene.hip", "ia_meshray.hip", "ia_scene_deep.hip", "ia_png.hip", "ia_lpips.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: fused multiply-adds appear only where the sources spell them
 # (IA_DOT3 / __builtin_fmaf), the same sequence the CPU checker uses
@@ -54,7 +54,8 @@ SHARED_HEADERS = [os.path.join(CSRC, "ia_common.h"), os.path.join(HERE, "..", "i
                   os.path.join(HERE, "..", "include", "instantavatar_hip_scene_receive.h"),
                   os.path.join(HERE, "..", "include", "instantavatar_hip_render_iter.h"),
                   os.path.join(HERE, "..", "include", "instantavatar_hip_scene_deep.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_png.h")]
+                  os.path.join(HERE, "..", "include", "instantavatar_hip_png.h"),
+                  os.path.join(HERE, "..", "include", "instantavatar_hip_lpips.h")]
 _MARK = b"IA_SOURCE_MANIFEST="
 
 

@@ -11,8 +11,13 @@ parameters to `<out>/poses/train.npz` for the train stage.
 layout then starts from `poses_optimized.npz` (custom.py:67-76), the PeopleSnapshot layout from its usual pose files.
 
 `fit_sequence(...)` takes any `DeviceFrames` (instantavatar_amd/datasets/device_frames.py); `--synthetic` builds one
-from the synthetic avatar with perturbed initial poses (no dataset ships with this package).  The LPIPS term of the
-reference's loss needs pretrained VGG weights and is not available offline (NGPLoss raises when asked for it).
+from the synthetic avatar with perturbed initial poses (no dataset ships with this package).
+
+The reference's fit configurations (confs/demo.yaml, confs/SNARF_NGP_fitting.yaml) set `w_lpips: 0.01` and `w_depth_reg: 0.01`:
+`--w-lpips 0.01 --lpips-lin third_parties/lpips/weights/v0.1/vgg.pth --lpips-trunk <a saved torchvision
+vgg16().features.state_dict()>` runs them (the two weight files cannot be fetched offline; without them the term stays off, the
+default).  `--patch-loss hip` evaluates the LPIPS and depth terms with the kernels of lpips_hip.py instead of torch ops and library
+convolutions: the step then stays on the seeded-gradient path of the rest of training.
 """
 import argparse
 import os
@@ -47,7 +52,7 @@ def build_fit_model(frames, body_model, device, threshold=0.05, n_levels=16):
 
 
 def fit_sequence(model, frames, steps, lr=1e-3, smpl_lr=1e-4, max_epochs=300, loss_opt=None, log_every=50, out=sys.stdout,
-                 generator=None, check_val_every_n_epoch=10, rank=0, world_size=1, graphed=True):
+                 generator=None, check_val_every_n_epoch=10, rank=0, world_size=1, graphed=True, lpips=None, patch_terms="torch"):
     """The optimisation loop of fit.py (trainer.fit with SNARF_NGP_fitting.yaml: Adam lr 1e-3, SMPL tables lr 1e-4, one frame
     per step; the LambdaLR steps once per validation run = every `check_val_every_n_epoch` epochs, DNeRF.py:163-166 -- see
     training.configure_scheduler).  Returns the last losses.
@@ -57,12 +62,13 @@ def fit_sequence(model, frames, steps, lr=1e-3, smpl_lr=1e-4, max_epochs=300, lo
     NOT a parity mode (the reference's fit.py is single-GPU): when the frame count is not a multiple of W the last step of an
     epoch wraps around, so the first frames of the shuffle are drawn twice in that epoch, and the moments of SMPL rows that got
     no gradient in a step still decay -- the optimisation trajectory differs from the 1-rank run's (same optimum, tested to
-    train: tests/test_gpu_drivers.py)."""
+    train: tests/test_gpu_drivers.py).
+    lpips / patch_terms: NGPLoss's arguments (a loaded utils.lpips.LPIPS for w_lpips > 0; "torch" or "hip" for the patch terms)."""
     from ..parallel import broadcast_module_state
     broadcast_module_state(model, world_size)
     opt = configure_optimizer(model, lr=lr, smpl_lr=smpl_lr)
     sched = configure_scheduler(opt, max_epochs)
-    loss_fn = NGPLoss(loss_opt or dict(w_rgb=1.0, w_alpha=0.1, w_reg=0.1, w_lpips=0.0, w_depth_reg=0.01))
+    loss_fn = NGPLoss(loss_opt or dict(w_rgb=1.0, w_alpha=0.1, w_reg=0.1, w_lpips=0.0, w_depth_reg=0.01), lpips=lpips, patch_terms=patch_terms)
     model.train()
     # graphed (one rank): the step is captured once (once per frame with `smpl_init`, where every frame has its own occupancy grid)
     # and replayed afterwards; occupancy-update steps and a capture that fails run eagerly (training.GraphedTrainStep)
@@ -135,9 +141,17 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--out", default="outputs/fit")
+    ap.add_argument("--w-lpips", type=float, default=0.0, help="weight of the LPIPS(VGG) term on the patches (the reference's fit configurations: 0.01)")
+    ap.add_argument("--w-depth-reg", type=float, default=0.01, help="weight of the depth regulariser on the patches")
+    ap.add_argument("--lpips-lin", help="third_parties/lpips/weights/v0.1/vgg.pth of a reference checkout")
+    ap.add_argument("--lpips-trunk", help="a saved torchvision vgg16().features.state_dict()")
+    ap.add_argument("--patch-loss", choices=("torch", "hip"), default="torch",
+                    help="the LPIPS and depth terms as torch ops and library convolutions, or as the HIP kernels of lpips_hip.py")
     args = ap.parse_args(argv)
     if bool(args.synthetic) + bool(args.frames) + bool(args.data) != 1:
         ap.error("exactly one of --synthetic / --frames <npz> / --data <dir> is required")
+    if args.w_lpips > 0 and not (args.lpips_lin and args.lpips_trunk):
+        ap.error("--lpips-lin and --lpips-trunk are both needed for the LPIPS term (--w-lpips > 0)")
     from .launch import Launch
     launch = Launch.from_env(who="fit")
     try:
@@ -159,7 +173,16 @@ def main(argv=None):
         else:
             frames, body_model, _ = synthetic_frames(device, res=args.res)
         model = build_fit_model(frames, body_model, device)
-        losses = fit_sequence(model, frames, args.steps, rank=launch.rank, world_size=launch.world_size, log_every=50 if launch.is_main else 0)
+        lp = None
+        if args.w_lpips > 0:
+            from ..utils.lpips import LPIPS
+            lp = LPIPS(net="vgg").load_lin_weights(args.lpips_lin).load_trunk_weights(args.lpips_trunk).to(device)
+        if launch.is_main:
+            print("patch terms (w_lpips %g, w_depth_reg %g): %s" % (args.w_lpips, args.w_depth_reg, {
+                "torch": "torch ops and library convolutions, autograd", "hip": "HIP kernels (lpips_hip), seeded gradients"}[args.patch_loss]))
+        loss_opt = dict(w_rgb=1.0, w_alpha=0.1, w_reg=0.1, w_lpips=args.w_lpips, w_depth_reg=args.w_depth_reg)
+        losses = fit_sequence(model, frames, args.steps, rank=launch.rank, world_size=launch.world_size, log_every=50 if launch.is_main else 0,
+                              loss_opt=loss_opt, lpips=lp, patch_terms=args.patch_loss)
         if launch.is_main:     # replicas are identical: rank 0 exports
             path = export_params(model, args.out)
             print("saved %s (mse %.5f, %d rank(s))" % (path, float(losses["mse_loss"]), launch.world_size))

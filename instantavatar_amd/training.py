@@ -398,10 +398,17 @@ class NGPLoss(NeRFLoss):
     depth-variance regulariser.  LPIPS (`utils.lpips.LPIPS`, VGG-16, v0.1) needs two weight files that cannot be
     fetched offline -- `opt.lpips_lin_weights` (third_parties/lpips/weights/v0.1/vgg.pth of a reference checkout) and
     `opt.lpips_vgg_weights` (torchvision's vgg16 feature weights saved with torch.save) -- or a ready module passed as
-    `lpips=`; `w_lpips > 0` without them raises instead of silently training against random features."""
+    `lpips=`; `w_lpips > 0` without them raises instead of silently training against random features.
+    patch_terms: "torch" (the default) evaluates the two patch terms with torch ops and library convolutions; "hip" evaluates them,
+    on CUDA patch batches, with the kernels of lpips_hip.py (csrc/ia_lpips.hip) -- `direct_backward_ok` then stays true with the
+    terms active and `value_and_grads` returns a fourth gradient, for `depth_coarse`."""
 
-    def __init__(self, opt=None, fused=True, lpips=None):
+    def __init__(self, opt=None, fused=True, lpips=None, patch_terms="torch"):
         super().__init__(opt, fused=fused)
+        if patch_terms not in ("torch", "hip"):
+            raise ValueError("NGPLoss: patch_terms must be 'torch' or 'hip', got %r" % (patch_terms,))
+        self.patch_terms = patch_terms
+        self._fused_lpips = None
         self.w_lpips = _opt.get(opt, "w_lpips", 0)
         self.w_depth_reg = _opt.get(opt, "w_depth_reg", 0)
         self.lpips = None
@@ -419,15 +426,61 @@ class NGPLoss(NeRFLoss):
             self.lpips = lpips
             for p in self.lpips.parameters():
                 p.requires_grad = False                                            # loss.py:12
+            if patch_terms == "hip":
+                from .lpips_hip import FusedLPIPS
+                self._fused_lpips = FusedLPIPS(self.lpips)                         # (refuses net="alex")
+
+    def _hip_patch_terms(self, predicts):
+        """the patch terms of this batch go through the HIP kernels: asked for, a patch batch, on the GPU"""
+        return self.patch_terms == "hip" and predicts["rgb_coarse"].dim() == 5 and predicts["rgb_coarse"].is_cuda
 
     def direct_backward_ok(self, predicts):
         patches = predicts["rgb_coarse"].dim() == 5
-        extra = patches and (self.w_lpips > 0 or self.w_depth_reg > 0)
+        extra = patches and (self.w_lpips > 0 or self.w_depth_reg > 0) and not self._hip_patch_terms(predicts)
         return bool(self.fused) and predicts["rgb_coarse"].is_cuda and not extra and type(self).forward is NGPLoss.forward
+
+    def value_and_grads(self, predicts, targets, overflow_src=None):
+        """NeRFLoss.value_and_grads; with patch_terms="hip" on a patch batch the two patch terms are added: `loss_lpips` and
+        `loss_depth_reg` in the dictionary, `loss` including them, and FOUR gradients -- w_lpips times the LPIPS gradient added to
+        d_rgb, w_depth_reg times the depth term's gradients added to d_alpha and returned for `depth_coarse`.  The overflow
+        poisoning is the loss kernel's: its NaN in `loss` and d_rgb survives the additions."""
+        losses, grads = super().value_and_grads(predicts, targets, overflow_src=overflow_src)
+        if not (self._hip_patch_terms(predicts) and (self.w_lpips > 0 or self.w_depth_reg > 0)):
+            return losses, grads
+        from . import lpips_hip
+        d_r, d_a, d_w = grads
+        loss = losses["loss"]
+        if self.w_lpips > 0:
+            values, g = self._fused_lpips.value_and_grad(predicts["rgb_coarse"].flatten(0, 1), targets["rgb"].flatten(0, 1))
+            lp = values.sum()
+            losses["loss_lpips"] = lp
+            loss = loss + self.w_lpips * lp
+            d_r = d_r.add(g.reshape(d_r.shape), alpha=float(self.w_lpips))
+        if self.w_depth_reg > 0:
+            reg, g_a, g_d = lpips_hip.depth_reg_value_and_grads(predicts["alpha_coarse"], predicts["depth_coarse"])
+            losses["loss_depth_reg"] = reg
+            loss = loss + self.w_depth_reg * reg
+            d_a = d_a.add(g_a.reshape(d_a.shape), alpha=float(self.w_depth_reg))
+            d_d = g_d.mul_(float(self.w_depth_reg)).reshape(predicts["depth_coarse"].shape)
+        else:
+            d_d = torch.zeros_like(predicts["depth_coarse"], dtype=torch.float32)
+        losses["loss"] = loss
+        return losses, (d_r, d_a, d_w, d_d)
 
     def forward(self, predicts, targets):
         losses = super().forward(predicts, targets)
         patches = predicts["rgb_coarse"].dim() == 5
+        if self._hip_patch_terms(predicts):
+            from . import lpips_hip
+            if self.w_lpips > 0:
+                lp = self._fused_lpips(predicts["rgb_coarse"].flatten(0, 1), targets["rgb"].flatten(0, 1)).sum()
+                losses["loss_lpips"] = lp
+                losses["loss"] = losses["loss"] + self.w_lpips * lp
+            if self.w_depth_reg > 0:
+                reg = lpips_hip.depth_reg(predicts["alpha_coarse"], predicts["depth_coarse"])
+                losses["loss_depth_reg"] = reg
+                losses["loss"] = losses["loss"] + self.w_depth_reg * reg
+            return losses
         if self.w_lpips > 0 and patches:                                           # loss.py:28-32 (BGR order, NCHW, clip)
             pr = predicts["rgb_coarse"][..., [2, 1, 0]].flatten(0, 1).permute(0, 3, 1, 2).clip(max=1)
             tg = targets["rgb"][..., [2, 1, 0]].flatten(0, 1).permute(0, 3, 1, 2)
@@ -650,7 +703,13 @@ def training_step(model, batch, optimizer, loss_fn, world_size=1, is_refine=Fals
             if not getattr(optimizer, "grads_zeroed", False):   # (a FusedAdam step with fused_zero_grad left every buffer zero-filled)
                 optimizer.zero_grad(set_to_none=True)
             if direct:
-                torch.autograd.backward([predicts["rgb_coarse"], predicts["alpha_coarse"], predicts["weight_coarse"]], list(grads))
+                seeds = [predicts["rgb_coarse"], predicts["alpha_coarse"], predicts["weight_coarse"]]
+                if len(grads) == 4:      # (NGPLoss(patch_terms="hip"): the depth regulariser's gradient seeds depth_coarse as well)
+                    if torch.is_tensor(predicts.get("depth_coarse")) and predicts["depth_coarse"].requires_grad:
+                        seeds.append(predicts["depth_coarse"])
+                    else:
+                        grads = grads[:3]
+                torch.autograd.backward(seeds, list(grads))
             else:
                 total = losses["loss"]
                 if overflow is not None:
