@@ -1,10 +1,11 @@
-"""ctypes binding of libinstantavatar_hip.so (the C ABI in include/instantavatar_hip.h).
+"""ctypes binding of libinstantavatar_hip.so (the C ABI in include/instantavatar_hip.h and its per-feature siblings).
 
 There is NO fallback: if the library is missing or a call fails, this raises.
-The header is the single source of the binding: `lib()` parses its prototypes (`parse_header`) and sets every function's
-restype / argtypes from them, and `call(name, *args)` -- the one way the package launches a kernel -- marshals its
-arguments against the same record: tensors as raw device pointers (checked: on the GPU, contiguous, of the dtype the
-pointee type admits), descriptor structs by reference, the current HIP stream when the caller leaves it out.
+The headers are the single source of the binding: `build.HEADERS` registers them, `lib()` parses their prototypes
+(`parse_header`) into one table and sets every function's restype / argtypes from it, and `call(name, *args)` -- the one
+way the package launches a kernel -- marshals its arguments against the same record: tensors as raw device pointers
+(checked: on the GPU, contiguous, of the dtype the pointee type admits), descriptor structs by reference, the current
+HIP stream when the caller leaves it out.
 """
 import collections
 import ctypes as C
@@ -12,6 +13,8 @@ import os
 import re
 
 import torch
+
+from . import build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libinstantavatar_hip.so")
@@ -54,67 +57,12 @@ class SmplBody(C.Structure):
     _fields_ = [("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p), ("lbs_weights", C.c_void_p),
                 ("J0", C.c_void_p), ("JS", C.c_void_p), ("parents", C.c_void_p), ("n_verts", C.c_int)]
 
-HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip.h")
-# the sequence-ingest entry points (csrc/ia_io.hip) are declared in a header of their own, parsed into a table of its own
-# (`io_declarations`): `declarations()` / `EXPORTED` stay the main header's set
-IO_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_io.h")
 
-# so are the surface-normal entry points (csrc/ia_normals.hip): `normals_declarations`
-NORMALS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_normals.h")
+def header_path(key="main"):
+    """Path of the registered C-ABI header `key`.  The registry (`build.HEADERS`) holds one key per header under include/;
+    the file name follows from the key (`build.header_name`)."""
+    return build.header_path(key)
 
-# and the mesh-extraction entry points (csrc/ia_isosurface.hip): `mesh_declarations`
-MESH_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_mesh.h")
-
-# and the rasteriser entry points (csrc/ia_raster.hip): `raster_declarations`
-RASTER_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_raster.h")
-
-# and the keypoint-refinement entry points (csrc/ia_keypoints.hip): `keypoints_declarations`
-KEYPOINTS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_keypoints.h")
-
-# and the soft-silhouette entry points (csrc/ia_silhouette.hip): `silhouette_declarations`
-SILHOUETTE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_silhouette.h")
-
-# and the mask-cleaning entry points (csrc/ia_masks.hip): `masks_declarations`
-MASKS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_masks.h")
-
-# and the sequence-inspection entry points (csrc/ia_overlay.hip): `overlay_declarations`
-OVERLAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_overlay.h")
-
-# and the mesh-processing entry points (csrc/ia_meshops.hip): `meshops_declarations`
-MESHOPS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_meshops.h")
-
-# and the texture-atlas entry points (csrc/ia_texture.hip): `texture_declarations`
-TEXTURE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_texture.h")
-
-# and the rigged-export entry points (csrc/ia_rig.hip): `rig_declarations`
-RIG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_rig.h")
-
-# and the surface-distance entry points (csrc/ia_meshdist.hip): `meshdist_declarations`
-MESHDIST_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_meshdist.h")
-
-# and the photo-texture entry points (csrc/ia_phototex.hip): `phototex_declarations`
-PHOTOTEX_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_phototex.h")
-
-# and the scene-composition entry points (csrc/ia_scene.hip): `scene_declarations`
-SCENE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_scene.h")
-
-# and the ray-query entry points (csrc/ia_meshray.hip): `meshray_declarations`
-MESHRAY_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_meshray.h")
-
-# and the shadow-receiving entry point of the scene composition (csrc/ia_scene.hip): `scene_receive_declarations`
-SCENE_RECEIVE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_scene_receive.h")
-
-# and the test-only entries of the inference wave-front loop's kernels (csrc/ia_render.hip): `render_iter_declarations`
-RENDER_ITER_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_render_iter.h")
-
-# and the per-sample compositor of the scene composition (csrc/ia_scene_deep.hip): `scene_deep_declarations`
-SCENE_DEEP_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_scene_deep.h")
-
-# and the PNG-encoding entry points (csrc/ia_png.hip): `png_declarations`
-PNG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_png.h")
-
-# and the patch-loss entry points (csrc/ia_lpips.hip): `lpips_declarations`
-LPIPS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "instantavatar_hip_lpips.h")
 
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long,
             "long long": C.c_longlong, "int32_t": C.c_int32}
@@ -171,10 +119,6 @@ def parse_header(text):
     return decls
 
 
-_decls = None
-_io_decls = None
-
-
 def _parse_file(path):
     try:
         with open(path) as f:
@@ -185,380 +129,33 @@ def _parse_file(path):
     return parse_header(text)
 
 
-def declarations():
-    """parse_header of this checkout's header, read once."""
-    global _decls
-    if _decls is None:
-        _decls = _parse_file(HEADER_PATH)
-    return _decls
-
-
-def io_declarations():
-    """parse_header of include/instantavatar_hip_io.h, read once: bound in `lib()` next to the main table and reachable
-    through `call`; its names are disjoint from the main header's."""
-    global _io_decls
-    if _io_decls is None:
-        d = _parse_file(IO_HEADER_PATH)
-        both = sorted(set(d) & set(declarations()))
-        if both:
-            raise ImportError("instantavatar_hip_io.h declares %s, which instantavatar_hip.h declares already" % ", ".join(both))
-        _io_decls = d
-    return _io_decls
-
-
-_normals_decls = None
-
-
-def normals_declarations():
-    """parse_header of include/instantavatar_hip_normals.h, read once: a third table, bound in `lib()` and reachable through
-    `call` like the other two; its names are disjoint from theirs."""
-    global _normals_decls
-    if _normals_decls is None:
-        d = _parse_file(NORMALS_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_normals.h declares %s, which another header declares already" % ", ".join(both))
-        _normals_decls = d
-    return _normals_decls
-
-
-_mesh_decls = None
-
-
-def mesh_declarations():
-    """parse_header of include/instantavatar_hip_mesh.h, read once: a fourth table, bound in `lib()` and reachable through
-    `call` like the other three; its names are disjoint from theirs."""
-    global _mesh_decls
-    if _mesh_decls is None:
-        d = _parse_file(MESH_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_mesh.h declares %s, which another header declares already" % ", ".join(both))
-        _mesh_decls = d
-    return _mesh_decls
-
-
-_raster_decls = None
-
-
-def raster_declarations():
-    """parse_header of include/instantavatar_hip_raster.h, read once: a fifth table, bound in `lib()` and reachable through
-    `call` like the other four; its names are disjoint from theirs."""
-    global _raster_decls
-    if _raster_decls is None:
-        d = _parse_file(RASTER_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_raster.h declares %s, which another header declares already" % ", ".join(both))
-        _raster_decls = d
-    return _raster_decls
-
-
-_keypoints_decls = None
-
-
-def keypoints_declarations():
-    """parse_header of include/instantavatar_hip_keypoints.h, read once: a sixth table, bound in `lib()` and reachable through
-    `call` like the other five; its names are disjoint from theirs."""
-    global _keypoints_decls
-    if _keypoints_decls is None:
-        d = _parse_file(KEYPOINTS_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_keypoints.h declares %s, which another header declares already" % ", ".join(both))
-        _keypoints_decls = d
-    return _keypoints_decls
-
-
-_silhouette_decls = None
-
-
-def silhouette_declarations():
-    """parse_header of include/instantavatar_hip_silhouette.h, read once: a seventh table, bound in `lib()` and reachable through
-    `call` like the other six; its names are disjoint from theirs."""
-    global _silhouette_decls
-    if _silhouette_decls is None:
-        d = _parse_file(SILHOUETTE_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_silhouette.h declares %s, which another header declares already" % ", ".join(both))
-        _silhouette_decls = d
-    return _silhouette_decls
-
-
-_masks_decls = None
-
-
-def masks_declarations():
-    """parse_header of include/instantavatar_hip_masks.h, read once: an eighth table, bound in `lib()` and reachable through
-    `call` like the other seven; its names are disjoint from theirs."""
-    global _masks_decls
-    if _masks_decls is None:
-        d = _parse_file(MASKS_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_masks.h declares %s, which another header declares already" % ", ".join(both))
-        _masks_decls = d
-    return _masks_decls
-
-
-_overlay_decls = None
-
-
-def overlay_declarations():
-    """parse_header of include/instantavatar_hip_overlay.h, read once: a ninth table, bound in `lib()` and reachable through
-    `call` like the other eight; its names are disjoint from theirs."""
-    global _overlay_decls
-    if _overlay_decls is None:
-        d = _parse_file(OVERLAY_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_overlay.h declares %s, which another header declares already" % ", ".join(both))
-        _overlay_decls = d
-    return _overlay_decls
-
-
-_meshops_decls = None
-
-
-def meshops_declarations():
-    """parse_header of include/instantavatar_hip_meshops.h, read once: a tenth table, bound in `lib()` and reachable through
-    `call` like the other nine; its names are disjoint from theirs."""
-    global _meshops_decls
-    if _meshops_decls is None:
-        d = _parse_file(MESHOPS_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_meshops.h declares %s, which another header declares already" % ", ".join(both))
-        _meshops_decls = d
-    return _meshops_decls
-
-
-_texture_decls = None
-
-
-def texture_declarations():
-    """parse_header of include/instantavatar_hip_texture.h, read once: an eleventh table, bound in `lib()` and reachable through
-    `call` like the other ten; its names are disjoint from theirs."""
-    global _texture_decls
-    if _texture_decls is None:
-        d = _parse_file(TEXTURE_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_texture.h declares %s, which another header declares already" % ", ".join(both))
-        _texture_decls = d
-    return _texture_decls
-
-
-_rig_decls = None
-
-
-def rig_declarations():
-    """parse_header of include/instantavatar_hip_rig.h, read once: a twelfth table, bound in `lib()` and reachable through
-    `call` like the other eleven; its names are disjoint from theirs."""
-    global _rig_decls
-    if _rig_decls is None:
-        d = _parse_file(RIG_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_rig.h declares %s, which another header declares already" % ", ".join(both))
-        _rig_decls = d
-    return _rig_decls
-
-
-_meshdist_decls = None
-
-
-def meshdist_declarations():
-    """parse_header of include/instantavatar_hip_meshdist.h, read once: a thirteenth table, bound in `lib()` and reachable through
-    `call` like the other twelve; its names are disjoint from theirs."""
-    global _meshdist_decls
-    if _meshdist_decls is None:
-        d = _parse_file(MESHDIST_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_meshdist.h declares %s, which another header declares already" % ", ".join(both))
-        _meshdist_decls = d
-    return _meshdist_decls
-
-
-_phototex_decls = None
-
-
-def phototex_declarations():
-    """parse_header of include/instantavatar_hip_phototex.h, read once: a fourteenth table, bound in `lib()` and reachable through
-    `call` like the other thirteen; its names are disjoint from theirs."""
-    global _phototex_decls
-    if _phototex_decls is None:
-        d = _parse_file(PHOTOTEX_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_phototex.h declares %s, which another header declares already" % ", ".join(both))
-        _phototex_decls = d
-    return _phototex_decls
-
-
-_scene_decls = None
-
-
-def scene_declarations():
-    """parse_header of include/instantavatar_hip_scene.h, read once: a fifteenth table, bound in `lib()` and reachable through
-    `call` like the other fourteen; its names are disjoint from theirs."""
-    global _scene_decls
-    if _scene_decls is None:
-        d = _parse_file(SCENE_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
-                                | set(phototex_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_scene.h declares %s, which another header declares already" % ", ".join(both))
-        _scene_decls = d
-    return _scene_decls
-
-
-_meshray_decls = None
-
-
-def meshray_declarations():
-    """parse_header of include/instantavatar_hip_meshray.h, read once: a sixteenth table, bound in `lib()` and reachable through
-    `call` like the other fifteen; its names are disjoint from theirs."""
-    global _meshray_decls
-    if _meshray_decls is None:
-        d = _parse_file(MESHRAY_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
-                                | set(phototex_declarations()) | set(scene_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_meshray.h declares %s, which another header declares already" % ", ".join(both))
-        _meshray_decls = d
-    return _meshray_decls
-
-
-_scene_receive_decls = None
-
-
-def scene_receive_declarations():
-    """parse_header of include/instantavatar_hip_scene_receive.h, read once: a seventeenth table, bound in `lib()` and reachable
-    through `call` like the other sixteen; its names are disjoint from theirs."""
-    global _scene_receive_decls
-    if _scene_receive_decls is None:
-        d = _parse_file(SCENE_RECEIVE_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
-                                | set(phototex_declarations()) | set(scene_declarations()) | set(meshray_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_scene_receive.h declares %s, which another header declares already" % ", ".join(both))
-        _scene_receive_decls = d
-    return _scene_receive_decls
-
-
-_render_iter_decls = None
-
-
-def render_iter_declarations():
-    """parse_header of include/instantavatar_hip_render_iter.h, read once: an eighteenth table, bound in `lib()` and reachable
-    through `call` like the other seventeen; its names are disjoint from theirs."""
-    global _render_iter_decls
-    if _render_iter_decls is None:
-        d = _parse_file(RENDER_ITER_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
-                                | set(phototex_declarations()) | set(scene_declarations()) | set(meshray_declarations())
-                                | set(scene_receive_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_render_iter.h declares %s, which another header declares already" % ", ".join(both))
-        _render_iter_decls = d
-    return _render_iter_decls
-
-
-_scene_deep_decls = None
-
-
-def scene_deep_declarations():
-    """parse_header of include/instantavatar_hip_scene_deep.h, read once: a nineteenth table, bound in `lib()` and reachable
-    through `call` like the other eighteen; its names are disjoint from theirs."""
-    global _scene_deep_decls
-    if _scene_deep_decls is None:
-        d = _parse_file(SCENE_DEEP_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
-                                | set(phototex_declarations()) | set(scene_declarations()) | set(meshray_declarations())
-                                | set(scene_receive_declarations()) | set(render_iter_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_scene_deep.h declares %s, which another header declares already" % ", ".join(both))
-        _scene_deep_decls = d
-    return _scene_deep_decls
-
-
-_png_decls = None
-
-
-def png_declarations():
-    """parse_header of include/instantavatar_hip_png.h, read once: a twentieth table, bound in `lib()` and reachable through
-    `call` like the other nineteen; its names are disjoint from theirs."""
-    global _png_decls
-    if _png_decls is None:
-        d = _parse_file(PNG_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
-                                | set(phototex_declarations()) | set(scene_declarations()) | set(meshray_declarations())
-                                | set(scene_receive_declarations()) | set(render_iter_declarations()) | set(scene_deep_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_png.h declares %s, which another header declares already" % ", ".join(both))
-        _png_decls = d
-    return _png_decls
-
-
-_lpips_decls = None
-
-
-def lpips_declarations():
-    """parse_header of include/instantavatar_hip_lpips.h, read once: a twenty-first table, bound in `lib()` and reachable through
-    `call` like the other twenty; its names are disjoint from theirs."""
-    global _lpips_decls
-    if _lpips_decls is None:
-        d = _parse_file(LPIPS_HEADER_PATH)
-        both = sorted(set(d) & (set(declarations()) | set(io_declarations()) | set(normals_declarations()) | set(mesh_declarations())
-                                | set(raster_declarations()) | set(keypoints_declarations()) | set(silhouette_declarations())
-                                | set(masks_declarations()) | set(overlay_declarations()) | set(meshops_declarations())
-                                | set(texture_declarations()) | set(rig_declarations()) | set(meshdist_declarations())
-                                | set(phototex_declarations()) | set(scene_declarations()) | set(meshray_declarations())
-                                | set(scene_receive_declarations()) | set(render_iter_declarations()) | set(scene_deep_declarations())
-                                | set(png_declarations())))
-        if both:
-            raise ImportError("instantavatar_hip_lpips.h declares %s, which another header declares already" % ", ".join(both))
-        _lpips_decls = d
-    return _lpips_decls
+_decls = {}      # header key -> its table, filled by `declarations`
+
+
+def declarations(key="main"):
+    """parse_header of this checkout's registered header `key`, read once.  Without a key: the main header's table."""
+    d = _decls.get(key)
+    if d is None:
+        d = _decls[key] = _parse_file(header_path(key))
+    return d
+
+
+def merge_tables(tables):
+    """One {function name: Decl} out of `(header file name, table)` pairs, in their order.  A name that two headers declare
+    is an error that names both of them."""
+    merged, owner = {}, {}
+    for fname, table in tables:
+        for name, d in table.items():
+            if name in owner:
+                raise ImportError("%s declares %s, which %s declares already" % (fname, name, owner[name]))
+            owner[name] = fname
+            merged[name] = d
+    return merged
+
+
+def merged_table():
+    """The prototypes of every registered header, in registry order: what `lib()` binds and `call` reaches."""
+    return merge_tables((build.header_name(k), declarations(k)) for k in build.HEADERS)
 
 
 def __getattr__(name):
@@ -584,7 +181,6 @@ def lib():
         # forget to rebuild, and every number is the OLD kernel's).  The manifest is read from the file's bytes; variants
         # built with IA_EXTRA_HIPCC_FLAGS carry the flags in their hashes, so the same variable must be set when they run.
         if os.environ.get("IA_ALLOW_STALE_LIB", "0") != "1":
-            from . import build
             have = build.library_manifest(LIB_PATH)
             try:
                 want = build.source_manifest()
@@ -598,13 +194,7 @@ def lib():
                     "instantavatar_amd: %s was built from other sources than this checkout (differs in: %s). Rebuild it "
                     "(`python -m instantavatar_amd.build`), or set IA_ALLOW_STALE_LIB=1 to run it anyway." % (LIB_PATH, ", ".join(diff)))
         l = C.CDLL(LIB_PATH)
-        for name, d in list(declarations().items()) + list(io_declarations().items()) + list(normals_declarations().items()) \
-                + list(mesh_declarations().items()) + list(raster_declarations().items()) + list(keypoints_declarations().items()) \
-                + list(silhouette_declarations().items()) + list(masks_declarations().items()) + list(overlay_declarations().items()) \
-                + list(meshops_declarations().items()) + list(texture_declarations().items()) + list(rig_declarations().items()) \
-                + list(meshdist_declarations().items()) + list(phototex_declarations().items()) + list(scene_declarations().items()) \
-                + list(meshray_declarations().items()) + list(scene_receive_declarations().items()) + list(render_iter_declarations().items()) \
-                + list(scene_deep_declarations().items()) + list(png_declarations().items()) + list(lpips_declarations().items()):
+        for name, d in merged_table().items():
             fn = getattr(l, name)  # AttributeError if a symbol is missing
             fn.restype = d.restype
             fn.argtypes = [p.ctype for p in d.params]
@@ -692,7 +282,8 @@ def call(name, *args):
         lib()
         f = _bound.get(name)
         if f is None:
-            raise IAError("%s is not declared in include/instantavatar_hip.h (nor in instantavatar_hip_io.h / instantavatar_hip_normals.h / instantavatar_hip_mesh.h / instantavatar_hip_raster.h / instantavatar_hip_keypoints.h / instantavatar_hip_silhouette.h / instantavatar_hip_masks.h / instantavatar_hip_overlay.h / instantavatar_hip_meshops.h / instantavatar_hip_texture.h / instantavatar_hip_rig.h / instantavatar_hip_meshdist.h / instantavatar_hip_phototex.h / instantavatar_hip_scene.h / instantavatar_hip_meshray.h / instantavatar_hip_scene_receive.h / instantavatar_hip_render_iter.h / instantavatar_hip_scene_deep.h / instantavatar_hip_png.h / instantavatar_hip_lpips.h)" % name)
+            files = [build.header_name(k) for k in build.HEADERS]
+            raise IAError("%s is not declared in include/%s (nor in %s)" % (name, files[0], " / ".join(files[1:])))
     fn, ptrs, n, has_stream, int_ret = f
     if len(args) != n:
         if has_stream and len(args) == n - 1:

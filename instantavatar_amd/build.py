@@ -35,27 +35,27 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # parity tests are bit-exact with it): 193.4 -> 191.7 us on a frame's sample points (profiles/r04_ab_search_variants.txt)
 TU_FLAGS = {"ia_search.hip": ["-fno-slp-vectorize"]}
 OBJCOPY = os.environ.get("LLVM_OBJCOPY", "/opt/rocm/lib/llvm/bin/llvm-objcopy")
-SHARED_HEADERS = [os.path.join(CSRC, "ia_common.h"), os.path.join(HERE, "..", "include", "instantavatar_hip.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_io.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_normals.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_mesh.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_raster.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_keypoints.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_silhouette.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_masks.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_overlay.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_meshops.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_texture.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_rig.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_meshdist.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_phototex.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_scene.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_meshray.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_scene_receive.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_render_iter.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_scene_deep.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_png.h"),
-                  os.path.join(HERE, "..", "include", "instantavatar_hip_lpips.h")]
+INCLUDE = os.path.join(HERE, "..", "include")
+# the C-ABI headers, one key each, in the order `_lib.lib()` binds them and `tu_hash` reads them.  Everything else about
+# a header is derived from its key: the file name (`header_name`), its path, its place in SHARED_HEADERS and its table
+# of prototypes in the binding (`_lib.declarations(key)`).  A new header is one more key at the end.
+HEADERS = ("main", "io", "normals", "mesh", "raster", "keypoints", "silhouette", "masks", "overlay", "meshops", "texture",
+           "rig", "meshdist", "phototex", "scene", "meshray", "scene_receive", "render_iter", "scene_deep", "png", "lpips")
+
+
+def header_name(key):
+    """file name of the registered header `key`: instantavatar_hip.h for "main", instantavatar_hip_<key>.h otherwise"""
+    if key not in HEADERS:
+        raise KeyError("%r is not a registered C-ABI header (build.HEADERS: %s)" % (key, ", ".join(HEADERS)))
+    return "instantavatar_hip.h" if key == "main" else "instantavatar_hip_%s.h" % key
+
+
+def header_path(key):
+    return os.path.join(INCLUDE, header_name(key))
+
+
+# what every translation unit's source hash covers (order and base names are inputs of `tu_hash`)
+SHARED_HEADERS = [os.path.join(CSRC, "ia_common.h")] + [header_path(k) for k in HEADERS]
 _MARK = b"IA_SOURCE_MANIFEST="
 
 

@@ -41,7 +41,7 @@ def inside_dirs():
     """[3,3] fp32: the three fixed ray directions of the inside test, as include/instantavatar_hip_meshray.h states them"""
     global _inside_dirs
     if _inside_dirs is None:
-        with open(_lib.MESHRAY_HEADER_PATH) as f:
+        with open(_lib.header_path("meshray")) as f:
             rows = re.findall(r"#define IA_MESHRAY_INSIDE_DIR_\d (.*)", f.read())
         _inside_dirs = np.array([[np.float32(x.strip().rstrip("f")) for x in r.split(",")] for r in rows], np.float32).reshape(3, 3)
     return _inside_dirs

@@ -368,19 +368,17 @@ def test_skinning_bound_covers_an_fp32_evaluation():
 
 
 # ---- the binding -------------------------------------------------------------------------------------------------------------------
-def test_rig_header_is_bound_as_a_twelfth_table():
+def test_rig_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    d = _lib.rig_declarations()
+    d = _lib.declarations("rig")
     assert sorted(d) == NAMES
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) \
-        | set(_lib.masks_declarations()) | set(_lib.overlay_declarations()) | set(_lib.meshops_declarations()) | set(_lib.texture_declarations())
-    assert not set(NAMES) & others and len(_lib.declarations()) == 89
+    assert len(_lib.declarations()) == 89
     for name in NAMES:
         assert d[name].stream, name                                                # every entry point launches and takes a stream
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     assert "ia_rig.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_rig.hip"))
-    assert os.path.normpath(_lib.RIG_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("rig")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_rig.hip" in build.source_manifest() and "ia_rig.hip" in build.library_manifest()
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_rig\.h"):
         _lib.call("ia_rig_export")

@@ -122,14 +122,13 @@ def test_obj_round_trip(tmp_path):
 
 def test_new_prototypes_are_declared_and_exported():
     from instantavatar_amd import _lib, build
-    decl = _lib.mesh_declarations()             # a header and a table of their own: include/instantavatar_hip_mesh.h
-    assert set(decl) == set(NEW)
-    assert not set(decl) & (set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()))
+    decl = _lib.declarations("mesh")            # a header of their own: include/instantavatar_hip_mesh.h
+    assert set(decl) == set(NEW)                # (disjoint from every other header's: tests/test_cpu_abi_headers.py)
     for name in NEW:
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
         assert decl[name].stream == (not name.endswith("_bytes")), name       # every launching entry point takes a stream
     assert "ia_isosurface.hip" in build.SOURCES
-    assert os.path.normpath(_lib.MESH_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("mesh")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     inc = [os.path.basename(h) for h in build.includes_of(os.path.join(build.CSRC, "ia_isosurface.hip"))]
     assert "ia_mt_table.h" in inc and "ia_search_dev.h" in inc               # an edit of either rebuilds the unit
     assert "ia_scan.h" in inc and "ia_mesh_dev.h" in inc                     # so does one of the mesh units' shared scan and face pieces

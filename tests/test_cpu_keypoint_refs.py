@@ -137,5 +137,5 @@ def test_the_module_constants_are_the_references_own():
     from instantavatar_amd import keypoints as K
     assert tuple(K.BODY25_TO_POINT) == tuple(kr.BODY25_TO_POINT) and tuple(K.SMPL_KP_VERTEX) == kr.SMPL_KP_VERTEX and K.MIDHIP == kr.MIDHIP
     from instantavatar_amd import _lib, build
-    assert os.path.normpath(_lib.KEYPOINTS_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS] and "ia_keypoints.hip" in build.SOURCES
-    assert sorted(_lib.keypoints_declarations()) == ["ia_kp_loss_bwd", "ia_kp_loss_fwd", "ia_kp_workspace_bytes"]
+    assert os.path.normpath(_lib.header_path("keypoints")) in [os.path.normpath(h) for h in build.SHARED_HEADERS] and "ia_keypoints.hip" in build.SOURCES
+    assert sorted(_lib.declarations("keypoints")) == ["ia_kp_loss_bwd", "ia_kp_loss_fwd", "ia_kp_workspace_bytes"]

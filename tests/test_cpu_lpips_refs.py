@@ -18,22 +18,14 @@ NAMES = ["ia_conv3x3", "ia_conv3x3_pack", "ia_conv3x3_packed_bytes", "ia_conv3x3
 
 def test_header_is_a_table_of_its_own_and_is_built():
     from instantavatar_amd import _lib, build
-    d = _lib.lpips_declarations()
-    assert sorted(d) == NAMES
-    others = [_lib.declarations, _lib.io_declarations, _lib.normals_declarations, _lib.mesh_declarations, _lib.raster_declarations,
-              _lib.keypoints_declarations, _lib.silhouette_declarations, _lib.masks_declarations, _lib.overlay_declarations,
-              _lib.meshops_declarations, _lib.texture_declarations, _lib.rig_declarations, _lib.meshdist_declarations,
-              _lib.phototex_declarations, _lib.scene_declarations, _lib.meshray_declarations, _lib.scene_receive_declarations,
-              _lib.render_iter_declarations, _lib.scene_deep_declarations, _lib.png_declarations]
-    assert len(others) == 20
-    for f in others:
-        assert not set(d) & set(f()), f.__name__
+    d = _lib.declarations("lpips")
+    assert sorted(d) == NAMES          # (disjoint from every other header's names: tests/test_cpu_abi_headers.py)
     for name in NAMES:
         if not name.endswith("_bytes"):
             assert d[name].stream, name
     assert len(d["ia_conv3x3"].params) == 14 and len(d["ia_patch_depth_reg"].params) == 8
     assert "ia_lpips.hip" in build.SOURCES and "ia_lpips.hip" in build.source_manifest()
-    assert os.path.normpath(_lib.LPIPS_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("lpips")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert os.path.exists(os.path.join(build.CSRC, "ia_lpips.hip"))
 
 

@@ -141,14 +141,12 @@ def test_apply():
 
 # ---- the binding table ------------------------------------------------------------------------------------------------------------------
 def test_masks_header_is_a_table_of_its_own():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    assert sorted(_lib.masks_declarations()) == ["ia_mask_apply", "ia_mask_clean", "ia_mask_clean_workspace_bytes"]
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations())
-    assert not set(_lib.masks_declarations()) & others
-    assert os.path.normpath(_lib.MASKS_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert sorted(_lib.declarations("masks")) == ["ia_mask_apply", "ia_mask_clean", "ia_mask_clean_workspace_bytes"]
+    assert os.path.normpath(_lib.header_path("masks")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_masks.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_masks.hip"))
-    d = _lib.masks_declarations()["ia_mask_clean"]
+    d = _lib.declarations("masks")["ia_mask_clean"]
     assert d.stream and [p.name for p in d.params][-3:] == ["ws", "ws_bytes", "stream"]
 
 

@@ -119,24 +119,21 @@ def percentile_rule():
 
 
 # ---- the binding ----------------------------------------------------------------------------------------------------------------------
-def test_meshdist_header_is_bound_as_a_thirteenth_table():
+def test_meshdist_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    d = _lib.meshdist_declarations()
+    d = _lib.declarations("meshdist")
     assert sorted(d) == NAMES
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) \
-        | set(_lib.masks_declarations()) | set(_lib.overlay_declarations()) | set(_lib.meshops_declarations()) | set(_lib.texture_declarations()) \
-        | set(_lib.rig_declarations())
-    assert not set(NAMES) & others and len(_lib.declarations()) == 89
+    assert len(_lib.declarations()) == 89
     for name in NAMES:
         assert d[name].stream == (name != "ia_meshdist_grid_workspace_bytes"), name
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     assert "ia_meshdist.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_meshdist.hip"))
-    assert os.path.normpath(_lib.MESHDIST_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("meshdist")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_meshdist.hip" in build.source_manifest() and "ia_meshdist.hip" in build.library_manifest()
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_meshdist\.h"):
         _lib.call("ia_meshdist_nothing")
-    text = open(_lib.MESHDIST_HEADER_PATH).read()
+    text = open(_lib.header_path("meshdist")).read()
     for cap in ("IA_MESHDIST_MAX_CELLS", "IA_MESHDIST_MAX_PAIRS"):
         assert "#define " + cap in text
 

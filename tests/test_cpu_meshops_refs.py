@@ -124,19 +124,16 @@ def test_vertex_normals_of_a_sphere_point_outwards():
 
 
 # ---- the binding --------------------------------------------------------------------------------------------------------------------
-def test_meshops_header_is_bound_as_a_tenth_table():
+def test_meshops_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    d = _lib.meshops_declarations()
+    d = _lib.declarations("meshops")
     assert sorted(d) == NAMES
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) \
-        | set(_lib.masks_declarations()) | set(_lib.overlay_declarations())
-    assert not set(NAMES) & others
     for name in NAMES:
         assert d[name].stream == (not name.endswith("_bytes")), name           # every launching entry point takes a stream
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     assert "ia_meshops.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_meshops.hip"))
-    assert os.path.normpath(_lib.MESHOPS_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("meshops")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_meshops\.h"):
         _lib.call("ia_mesh_edge_collapse")
 

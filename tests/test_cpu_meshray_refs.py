@@ -14,7 +14,7 @@ NAMES = ["ia_meshray_closest", "ia_meshray_count"]
 
 def _header():
     from instantavatar_amd import _lib
-    with open(_lib.MESHRAY_HEADER_PATH) as f:
+    with open(_lib.header_path("meshray")) as f:
         return f.read()
 
 
@@ -154,22 +154,18 @@ def test_the_fan_rays_are_clear():
 
 
 # ---- the binding ------------------------------------------------------------------------------------------------------------------------
-def test_meshray_header_is_bound_as_a_sixteenth_table():
+def test_meshray_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    d = _lib.meshray_declarations()
+    d = _lib.declarations("meshray")
     assert sorted(d) == NAMES
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) \
-        | set(_lib.masks_declarations()) | set(_lib.overlay_declarations()) | set(_lib.meshops_declarations()) | set(_lib.texture_declarations()) \
-        | set(_lib.rig_declarations()) | set(_lib.meshdist_declarations()) | set(_lib.phototex_declarations()) | set(_lib.scene_declarations())
-    assert not set(NAMES) & others
     for name in NAMES:
         assert d[name].stream, name
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     assert [p.name for p in d["ia_meshray_count"].params[-4:]] == ["limit", "count", "tests", "stream"]
     assert [p.name for p in d["ia_meshray_closest"].params[:5]] == ["origins", "dirs", "t_min", "t_max", "P"]
     assert "ia_meshray.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_meshray.hip"))
-    assert os.path.normpath(_lib.MESHRAY_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("meshray")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_meshray.hip" in build.source_manifest() and "ia_meshray.hip" in build.library_manifest()
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_meshray\.h"):
         _lib.call("ia_meshray_nothing")

@@ -13,8 +13,8 @@ NEW = ("ia_surface_points_workspace_bytes", "ia_surface_points", "ia_field_sigma
 
 def test_new_prototypes_are_declared_and_exported():
     from instantavatar_amd import _lib
-    decl = _lib.normals_declarations()          # a header and a table of their own: include/instantavatar_hip_normals.h
-    assert set(decl) == set(NEW) and not set(decl) & (set(_lib.declarations()) | set(_lib.io_declarations()))
+    decl = _lib.declarations("normals")         # a header of their own: include/instantavatar_hip_normals.h
+    assert set(decl) == set(NEW)                # (disjoint from every other header's: tests/test_cpu_abi_headers.py)
     for name in NEW:
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     for name in NEW[1:]:
@@ -24,7 +24,7 @@ def test_new_prototypes_are_declared_and_exported():
     assert "ia_normals.hip" in build.SOURCES
     for unit in ("ia_field.hip", "ia_normals.hip"):      # an edit of the shared device header invalidates both source hashes
         assert "ia_field_dev.h" in [os.path.basename(h) for h in build.includes_of(os.path.join(build.CSRC, unit))], unit
-    assert os.path.normpath(_lib.NORMALS_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("normals")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
 
 
 def test_cpu_tensors_raise():

@@ -131,20 +131,18 @@ def test_stats_and_shade_literals():
 
 
 # ---- the binding and the tables ---------------------------------------------------------------------------------------------------------
-def test_overlay_header_is_bound_as_a_ninth_table():
+def test_overlay_header_is_declared_and_built():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
     names = ["ia_overlay_blend", "ia_overlay_face_shade", "ia_overlay_outline", "ia_overlay_skeleton", "ia_overlay_stats",
              "ia_overlay_stats_workspace_bytes"]
-    assert sorted(_lib.overlay_declarations()) == names
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) | set(_lib.masks_declarations())
-    assert not set(names) & others
-    assert os.path.normpath(_lib.OVERLAY_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert sorted(_lib.declarations("overlay")) == names
+    assert os.path.normpath(_lib.header_path("overlay")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_overlay.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_overlay.hip"))
     for name in names:
-        d = _lib.overlay_declarations()[name]
+        d = _lib.declarations("overlay")[name]
         assert d.stream == (name != "ia_overlay_stats_workspace_bytes"), name
-    d = _lib.overlay_declarations()["ia_overlay_skeleton"]
+    d = _lib.declarations("overlay")["ia_overlay_skeleton"]
     assert [p.name for p in d.params][:3] == ["points", "n", "K"] and d.params[9].name == "threshold" and d.params[9].kind == "scalar"
 
 

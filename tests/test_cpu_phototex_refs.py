@@ -187,21 +187,17 @@ def test_the_scenes_of_the_kernel_test_leave_at_most_one_percent_undecided(nf, B
 
 
 # ---- the binding --------------------------------------------------------------------------------------------------------------------
-def test_phototex_header_is_bound_as_a_fourteenth_table():
+def test_phototex_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    d = _lib.phototex_declarations()
+    d = _lib.declarations("phototex")
     assert sorted(d) == NAMES
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) \
-        | set(_lib.masks_declarations()) | set(_lib.overlay_declarations()) | set(_lib.meshops_declarations()) | set(_lib.texture_declarations()) \
-        | set(_lib.rig_declarations()) | set(_lib.meshdist_declarations())
-    assert not set(NAMES) & others
     assert len(_lib.declarations()) == 89
     for name in NAMES:
         assert d[name].stream == (name != "ia_phototex_acc_bytes"), name       # every launching entry point takes a stream
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     assert "ia_phototex.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_phototex.hip"))
-    assert os.path.normpath(_lib.PHOTOTEX_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("phototex")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_phototex.hip" in build.source_manifest() and "ia_phototex.hip" in build.library_manifest()
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_phototex\.h"):
         _lib.call("ia_phototex_nothing")

@@ -175,13 +175,13 @@ def test_package_framing_equals_the_reference():
 
 def test_binding_table_bound_and_host_side_refusals():
     from instantavatar_amd import _lib, build
-    d = _lib.png_declarations()
+    d = _lib.declarations("png")
     assert sorted(d) == ["ia_png_bound_bytes", "ia_png_encode", "ia_png_strips", "ia_png_workspace_bytes"]
     assert d["ia_png_encode"].stream and len(d["ia_png_encode"].params) == 15
     assert hasattr(_lib.lib(), "ia_png_encode") and "ia_png_encode" in _lib._bound
     assert "ia_png.hip" in build.SOURCES and "ia_png.hip" in build.source_manifest() and "ia_png.hip" in build.library_manifest()
-    assert os.path.normpath(_lib.PNG_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
-    with open(_lib.PNG_HEADER_PATH) as f:
+    assert os.path.normpath(_lib.header_path("png")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    with open(_lib.header_path("png")) as f:
         text = f.read()
     assert "#define IA_PNG_DEFAULT_STRIP_ROWS %d" % pr.DEFAULT_STRIP_ROWS in text and "#define IA_PNG_MAX_STRIP_BYTES %d" % pr.MAX_STRIP_BYTES in text
     # the bound is a closed expression: the C function and the reference agree, and the default strip fits 1920 x 4 bytes

@@ -179,14 +179,13 @@ def test_interpolation_reproduces_linear_functions():
 # ---- declarations and build plumbing ----------------------------------------------------------------------------------
 def test_raster_prototypes_are_declared_and_exported():
     from instantavatar_amd import _lib, build
-    decl = _lib.raster_declarations()             # a header and a table of their own: include/instantavatar_hip_raster.h
-    assert set(decl) == set(NEW)
-    assert not set(decl) & (set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()))
+    decl = _lib.declarations("raster")            # a header of their own: include/instantavatar_hip_raster.h
+    assert set(decl) == set(NEW)                  # (disjoint from every other header's: tests/test_cpu_abi_headers.py)
     for name in NEW:
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
         assert decl[name].stream == (not name.endswith("_bytes")), name       # every launching entry point takes a stream
     assert "ia_raster.hip" in build.SOURCES
-    assert os.path.normpath(_lib.RASTER_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("raster")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_raster.hip" in build.source_manifest()
 
 

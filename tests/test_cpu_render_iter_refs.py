@@ -216,15 +216,16 @@ def test_init_and_finalize_references():
     assert rr.finalize_ref(np.zeros((2, 3), F), np.zeros(2, F), np.ones(2, F), np.zeros(2, F), None, [5, 0, 0, 63, 7, 0, 0, 0], 64)["n_alive_out"].tolist() == [5, 7]
 
 
-def test_render_iter_header_is_bound_as_an_eighteenth_table():
+def test_render_iter_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     import os
     from instantavatar_amd import _lib, build
-    d = _lib.render_iter_declarations()
+    d = _lib.declarations("render_iter")
     assert sorted(d) == ["ia_render_composite_compact", "ia_render_finalize", "ia_render_init_rays", "ia_render_march_compact"]
-    assert all(v.stream for v in d.values()) and not set(d) & set(_lib.declarations())
+    assert all(v.stream for v in d.values())
     assert [p.name for p in d["ia_render_finalize"].params] == ["R", "color", "depth", "nohit", "counter", "bg", "state_end", "max_samples", "n_alive_out",
                                                                 "rgb", "depth_out", "alpha", "counter_out", "stream"]
-    assert os.path.normpath(_lib.RENDER_ITER_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("render_iter")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     L = _lib.lib()
     assert all(n in _lib._bound for n in d)
     # the argument checks run before anything touches the GPU

@@ -243,15 +243,15 @@ def test_the_cases_contain_what_they_claim():
 
 def test_binding_table():
     from instantavatar_amd import _lib, build
-    d = _lib.scene_deep_declarations()
+    d = _lib.declarations("scene_deep")
     assert sorted(d) == ["ia_scene_deep_composite"] and d["ia_scene_deep_composite"].stream and len(d["ia_scene_deep_composite"].params) == 20
     assert hasattr(_lib.lib(), "ia_scene_deep_composite") and "ia_scene_deep_composite" in _lib._bound
     assert "ia_scene_deep.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_scene_deep.hip"))
-    assert os.path.normpath(_lib.SCENE_DEEP_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("scene_deep")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_scene_deep.hip" in build.source_manifest() and "ia_scene_deep.hip" in build.library_manifest()
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_scene_deep\.h"):
         _lib.call("ia_scene_nothing")
-    with open(_lib.SCENE_DEEP_HEADER_PATH) as f:
+    with open(_lib.header_path("scene_deep")) as f:
         assert "#define IA_SCENE_DEEP_MAX_SLOTS %d" % sdr.MAX_SLOTS in f.read()
 
 

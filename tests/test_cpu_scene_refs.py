@@ -232,25 +232,21 @@ def test_shadow_bilinear_pcf_and_the_product_over_layers():
 
 
 # ---- the binding ------------------------------------------------------------------------------------------------------------------------
-def test_scene_header_is_bound_as_a_fifteenth_table():
+def test_scene_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    d = _lib.scene_declarations()
+    d = _lib.declarations("scene")
     assert sorted(d) == NAMES
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) \
-        | set(_lib.masks_declarations()) | set(_lib.overlay_declarations()) | set(_lib.meshops_declarations()) | set(_lib.texture_declarations()) \
-        | set(_lib.rig_declarations()) | set(_lib.meshdist_declarations()) | set(_lib.phototex_declarations())
-    assert not set(NAMES) & others
     assert len(_lib.declarations()) == 89
     for name in NAMES:
         assert d[name].stream, name                                       # every entry point launches and takes a stream
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     assert "ia_scene.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_scene.hip"))
-    assert os.path.normpath(_lib.SCENE_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("scene")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_scene.hip" in build.source_manifest() and "ia_scene.hip" in build.library_manifest()
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_scene\.h"):
         _lib.call("ia_scene_nothing")
-    with open(_lib.SCENE_HEADER_PATH) as f:
+    with open(_lib.header_path("scene")) as f:
         assert "#define IA_SCENE_MAX_LAYERS %d" % sr.MAX_LAYERS in f.read()
 
 

@@ -156,14 +156,15 @@ def test_split_options_reads_a_reference_dataset_config(tmp_path):
         sd.split_options(conf, "val")
 
 
-def test_the_second_header_is_a_table_of_its_own():
+def test_the_io_header_is_declared_and_built():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    io = _lib.io_declarations()
+    io = _lib.declarations("io")
     assert list(io) == ["ia_io_ingest_chunk"] and io["ia_io_ingest_chunk"].stream
     assert [p.name for p in io["ia_io_ingest_chunk"].params] == ["src_images", "src_masks", "mask_form", "n", "H0", "W0", "factor", "images",
                                                                  "masks", "first", "n_frames", "stream"]
     main = _lib.declarations()
-    assert not set(io) & set(main) and len(main) == 89 and set(_lib.EXPORTED) == set(main)
-    assert os.path.normpath(_lib.IO_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS] and "ia_io.hip" in build.SOURCES
+    assert len(main) == 89 and set(_lib.EXPORTED) == set(main)
+    assert os.path.normpath(_lib.header_path("io")) in [os.path.normpath(h) for h in build.SHARED_HEADERS] and "ia_io.hip" in build.SOURCES
     _lib.lib()
     assert "ia_io_ingest_chunk" in _lib._bound          # bound next to the main table: reachable through `_lib.call`

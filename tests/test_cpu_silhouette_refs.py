@@ -159,12 +159,10 @@ def test_edge_cases_skip_what_the_definition_skips():
 
 def test_the_new_entries_are_declared_and_registered():
     from instantavatar_amd import _lib, build
-    assert sorted(_lib.silhouette_declarations()) == ["ia_sil_body_bwd", "ia_sil_body_workspace_bytes", "ia_sil_project_bwd", "ia_sil_project_fwd",
-                                                      "ia_sil_render_bwd", "ia_sil_render_fwd", "ia_sil_workspace_bytes"]
-    others = (set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations())
-              | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()))
-    assert not set(_lib.silhouette_declarations()) & others
-    assert os.path.normpath(_lib.SILHOUETTE_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert sorted(_lib.declarations("silhouette")) == ["ia_sil_body_bwd", "ia_sil_body_workspace_bytes", "ia_sil_project_bwd", "ia_sil_project_fwd",
+                                                       "ia_sil_render_bwd", "ia_sil_render_fwd", "ia_sil_workspace_bytes"]
+    # (disjoint from every other header's names: tests/test_cpu_abi_headers.py)
+    assert os.path.normpath(_lib.header_path("silhouette")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_silhouette.hip" in build.SOURCES
 
 

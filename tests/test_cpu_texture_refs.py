@@ -211,19 +211,16 @@ def test_reference_bake_of_a_sphere_snaps_every_texel():
 
 
 # ---- the binding --------------------------------------------------------------------------------------------------------------------
-def test_texture_header_is_bound_as_an_eleventh_table():
+def test_texture_header_is_bound():
+    """(that its names are disjoint from every other header's: tests/test_cpu_abi_headers.py)"""
     from instantavatar_amd import _lib, build
-    d = _lib.texture_declarations()
+    d = _lib.declarations("texture")
     assert sorted(d) == NAMES
-    others = set(_lib.declarations()) | set(_lib.io_declarations()) | set(_lib.normals_declarations()) | set(_lib.mesh_declarations()) \
-        | set(_lib.raster_declarations()) | set(_lib.keypoints_declarations()) | set(_lib.silhouette_declarations()) \
-        | set(_lib.masks_declarations()) | set(_lib.overlay_declarations()) | set(_lib.meshops_declarations())
-    assert not set(NAMES) & others
     for name in NAMES:
         assert d[name].stream == (name != "ia_tex_atlas_size"), name           # every launching entry point takes a stream
         assert hasattr(_lib.lib(), name) and name in _lib._bound, name
     assert "ia_texture.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ia_texture.hip"))
-    assert os.path.normpath(_lib.TEXTURE_HEADER_PATH) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
+    assert os.path.normpath(_lib.header_path("texture")) in [os.path.normpath(h) for h in build.SHARED_HEADERS]
     assert "ia_texture.hip" in build.source_manifest() and "ia_texture.hip" in build.library_manifest()
     with pytest.raises(_lib.IAError, match=r"instantavatar_hip_texture\.h"):
         _lib.call("ia_tex_unwrap")

@@ -58,7 +58,7 @@ def _same(a, b, keys=KEYS):
 
 def _dirs():
     from instantavatar_amd import _lib
-    with open(_lib.MESHRAY_HEADER_PATH) as f:
+    with open(_lib.header_path("meshray")) as f:
         return mr.inside_dirs(f.read())
 
 
